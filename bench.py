@@ -7,13 +7,17 @@ teacher output, backward, grad-norm and AdamW -- all on the HIP path, replayed f
 (weights, the 128x2048 activation banks) are resident in HBM before the timed region.
 
     python bench.py --gpus N --steps K --warmup W [--config llama-7b-w4a4|llama-7b-w3a16g128|...]
+                    [--dump-outputs DIR] [--full]
 
 Two timed regions, both bracketed by barrier + synchronize and reduced with MAX over ranks:
   1. the contract's region: W warm-up + exactly K sample-steps per rank (`value`, `ms_per_step`).  There is no
      collective inside the step loop of the layer-sharded engine, so every rank steps its own block;
-  2. `end_to_end`: the REAL sharded engine (omniquant_amd.parallel.calibrate_sharded over world x blocks-per-rank
-     layers): streamed teacher pre-pass with RCCL send/recv of the boundary activation bank, per-layer teacher pass,
-     hipGraph capture, the sample-steps, fold, propagate and the final parameter gather.
+  2. `end_to_end` (--full only): the REAL sharded engine (omniquant_amd.parallel.calibrate_sharded over world x
+     blocks-per-rank layers): streamed teacher pre-pass with RCCL send/recv of the boundary activation bank, per-layer
+     teacher pass, hipGraph capture, the sample-steps, fold, propagate and the final parameter gather.
+A plain run sets up, warms up, times region 1 and prints its line.  --full adds what takes runs of its own: the
+per-kernel rooflines (an eager pass of the step under HIP events), region 2 and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0's block) as DIR/<name>.npy.
 N>1: launched by torch.distributed.run, one rank per GPU.  Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -265,6 +269,33 @@ def pmc_counters(name):
     return ent.get("bytes_per_launch"), ent.get("mfma_busy_frac"), src
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 20       # per array: the grouped LWC bounds of llama-2-70b-w2a16g64 alone are 102 MB
+
+
+def dump_outputs(path, runner, opt):
+    """What the last sample-step hands its caller, as float32 .npy files: the loss, the gradient norm and every learnable
+    of the block after the step's AdamW update (LWC bounds, LET scales and shifts; `param.<name>`).  Called straight after
+    the timed loop, before anything else steps the block.  An array of more than DUMP_MAX_ELEMS elements is written as a
+    fixed sample: the same seeded DUMP_MAX_ELEMS flat indices, in increasing order, in every run."""
+    import numpy as np
+    arrays = {"loss": runner.loss, "grad_norm": opt.norm[:1]}
+    arrays.update(("param." + n, p) for n, p in opt.named)
+    out = {}
+    for n, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            a = a.reshape(-1)[idx]
+        out[n] = a.numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(path, n + ".npy"), a)
+
+
 def cpu_baseline(name, n_steps=3, n_warm=1):
     """CPU baseline: the oracle (pure-PyTorch fp32 restatement of the reference loop, pinned to the reference by the
     golden fixtures) timed on this box's host cores on a bounded sample of the SAME workload.  Baseline only."""
@@ -394,12 +425,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=256)
     ap.add_argument("--config", default="llama-7b-w4a4", choices=list(CONFIGS))
     ap.add_argument("--nsamples", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also measure the per-kernel rooflines, the end-to-end region and the "
+                                                        "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the end-to-end region")
     ap.add_argument("--e2e-samples", type=int, default=16, help="calibration samples of the end-to-end region")
     ap.add_argument("--blocks-per-rank", type=int, default=1, help="decoder blocks per rank in the end-to-end region")
     ap.add_argument("--boundary-chunk", type=int, default=4, help="samples per boundary message of the teacher pre-pass")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start one fresh process per GPU and relay rank 0's JSON line.  Nothing in this
@@ -444,6 +480,12 @@ def main():
 
     aug = CONFIGS[a.config][8]          # --aug_loss: the step also reads fp_inps_2 (= the teacher output of the student input; with
     fp2 = fp_inps if aug else None      # identical synthetic banks that is the same tensor as fp_inps)
+    # capture the step's hipGraph here, with the first sample in the step's buffers as the first run() would have it, so that
+    # no warm-up or timed step pays for the capture
+    for src, dst in ((quant_inps, runner.x), (fp_inps, runner.t1), (fp2, runner.t2)):
+        if dst is not None:
+            dst.copy_(src[:1])
+    runner._capture()
     for j in range(a.warmup):
         runner.run(quant_inps[j % n:j % n + 1], fp_inps[j % n:j % n + 1], fp2[j % n:j % n + 1] if aug else None)
     sync()
@@ -458,14 +500,15 @@ def main():
         dt = float(tmax)
     loss = float(runner.loss)
     assert loss == loss, "NaN loss in the timed region"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, runner, opt)
 
-    roof = kernel_rooflines(runner, quant_inps, fp_inps, cfg)
+    from omniquant_amd.calibrate import get_named_linears
+    int_fprop = any(m.int_fprop_eligible(q.compute_dtype) for m in get_named_linears(q).values())
     out = None
     if rank == 0:
         flops, P = linear_flops(cfg, SEQLEN)
         value = world * a.steps / dt
-        traffic, mfma_busy, src = pmc_counters(a.config)
-        b16, i8 = roof["bf16"], roof["int8"]
         out = {
             "metric": "calibration_sample_steps_per_sec", "value": value, "unit": "sample-steps/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
@@ -475,7 +518,21 @@ def main():
                        "n_ranks_seen": int(dist.get_world_size()) if dist is not None else 1,
                        "per_gpu_sample_steps_per_sec": value / world, "last_loss": loss,
                        "linear_tflop_per_step": flops / 1e12,
-                       "fprop_arithmetic": "int8 codes on v_mfma_i32_16x16x64_i8 (exact), fp32 epilogue" if i8 else "bf16"},
+                       "fprop_arithmetic": "int8 codes on v_mfma_i32_16x16x64_i8 (exact), fp32 epilogue" if int_fprop else "bf16"},
+        }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    roof = kernel_rooflines(runner, quant_inps, fp_inps, cfg)
+    if rank == 0:
+        traffic, mfma_busy, src = pmc_counters(a.config)
+        b16, i8 = roof["bf16"], roof["int8"]
+        out.update({
             # dominant kernel of the step: the bf16 MFMA GEMM (dgrad + wgrad of the fake-quant linears; + fprop when the integer
             # path is off).  achieved = algorithmic flops of those launches / their summed HIP-event durations.
             "roofline": {"bound": "mfma", "kernel": ROOFLINE_KERNEL + (" (dgrad + wgrad of the fake-quant linears)" if i8 else
@@ -487,7 +544,7 @@ def main():
                          "linear_gemm_ms_per_step": b16["ms_per_step"], "tflop_per_step": b16["tflop_per_step"],
                          "all_gemm_ms_per_step": roof["gemm_ms_per_step"],
                          "event_pair_overhead_us_subtracted": roof["event_pair_overhead_us"]},
-        }
+        })
         if i8:
             out["roofline_int8"] = {"bound": "mfma", "kernel": "gemm_i8_p3_kernel (fprop of the fake-quant linears on integer codes)",
                                     "achieved": i8["tflops"], "peak": MFMA_I8_PEAK_TOPS, "unit": "TOP/s",

@@ -10,7 +10,15 @@ import torch
 from conftest import GOLDEN, load_golden
 from oracle import ref_cpu as R
 
-torch.set_num_threads(4)
+
+@pytest.fixture(autouse=True)
+def _four_threads():
+    """The oracle's fp32 sums are compared at 4 threads.  Set per test, not once at import: a test that runs earlier in the
+    same session (tests/test_fullsize_parity.py) sets the process-wide thread count to the host's cores."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(4)
+    yield
+    torch.set_num_threads(n)
 
 
 def T(a):

@@ -6,17 +6,17 @@ HEAD=${1:-unknown}
 out=gpurun_out/final
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py > $out/r3_bench_default.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python bench.py --steps 64 --warmup 16 --no-cpu-baseline --no-end-to-end > $out/prof.log 2>&1
+python bench.py --full > $out/r3_bench_default.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python bench.py --full --steps 64 --warmup 16 --no-cpu-baseline --no-end-to-end > $out/prof.log 2>&1
 cp $(find $out/prof -name "*kernel_stats.csv" | head -1) $out/r3_bench_kernel_stats.csv
 python tools/step_profile.py $(find $out/prof -name "*kernel_trace.csv" | head -1) 80 > $out/r3_step_breakdown.txt
 rm -rf $out/prof
 for c in llama-7b-w3a16g128 llama-2-13b-w4a4 llama-2-70b-w2a16g64; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$c -o bench -- python bench.py --config $c --steps 32 --warmup 8 --no-cpu-baseline --no-end-to-end > $out/prof_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$c -o bench -- python bench.py --full --config $c --steps 32 --warmup 8 --no-cpu-baseline --no-end-to-end > $out/prof_$c.log 2>&1
   python tools/step_profile.py $(find $out/prof_$c -name "*kernel_trace.csv" | head -1) 80 > $out/r3_step_breakdown_$c.txt
   rm -rf $out/prof_$c
 done
-P="python bench.py --steps 4 --warmup 1 --nsamples 4 --no-cpu-baseline --no-end-to-end"
+P="python bench.py --full --steps 4 --warmup 1 --nsamples 4 --no-cpu-baseline --no-end-to-end"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $out/mfma -o p -- $P > $out/mfma.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -o p -- $P > $out/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -o p -- $P > $out/write.log 2>&1
@@ -31,7 +31,7 @@ rm -rf $out/mfma $out/fetch $out/write $out/sq
 OQ_MB_CODES=1 python tools/microbench_rowq.py > $out/r3_quant_microbench.txt 2>&1
 python tools/microbench_gemm_i8.py > $out/r3_gemm_i8_microbench.txt 2>&1
 python tools/microbench_wgrad.py > $out/r3_wgrad_microbench.txt 2>&1
-for c in llama-7b-w4a4-aug llama-7b-w3a16g128 llama-2-13b-w4a4 llama-2-70b-w2a16g64 opt-125m-w4a16; do python bench.py --config $c --steps 256 --warmup 32 --no-cpu-baseline 2>/dev/null; done > $out/r3_bench_configs.jsonl
+for c in llama-7b-w4a4-aug llama-7b-w3a16g128 llama-2-13b-w4a4 llama-2-70b-w2a16g64 opt-125m-w4a16; do python bench.py --full --config $c --steps 256 --warmup 32 --no-cpu-baseline 2>/dev/null; done > $out/r3_bench_configs.jsonl
 {
   for kv in "OQ_INT_FPROP 0 1" "OQ_GEMM_W256 0 1" "OQ_INT_PRE_F32_QKV 0 1" "OQ_INT_PRE_F32_MLP 0 1" "OQ_GRID_ATTN 0 1" "OQ_WIDE 0 1"; do
     set -- $kv
