@@ -287,6 +287,28 @@ int oq_act_stats(const void* x, int dtype, int64_t nsamp, int64_t rows, int64_t 
 int oq_pack_weights(const void* w, int dtype, int64_t out, int64_t in, int64_t group, int bits, const float* scales,
                     const float* zeros, int32_t* qweight, int32_t* qzeros, void* stream);
 
+/* ---- real-quant inference on the packed buffers (quantize/omniquant.py:255-278 packs them; main.py:364 evaluates the packed
+ *      model through AutoGPTQ's QuantLinear.forward -- parity unpinned, see csrc/oq_packed.hip).  qweight / qzeros / scales
+ *      [in/group, out] fp16 exactly as oq_pack_weights writes them, g_idx = arange(in) / group (act-order is not supported);
+ *      bias fp16 [out] or NULL.  bits 2, 3, 4 or 8; in % 32 == 0, out % 32 == 0; group == in or a divisor of in that is a
+ *      multiple of 32 (anything else: OQ_E_ARG).  Weight value = fp16(scale * (q - (zq + 1))) (PackedLinear.dequantize()),
+ *      rounded once more to bf16 when the activations are bf16.
+ *   oq_packed_dequant: w [out, in] in w_dtype (f32 / fp16 / bf16); fp16 output is bit-exact with dequantize().
+ *   oq_packed_gemv:    y[M,out] = x[M,in] . W^T (+ bias) (+ addend), x / y / addend fp16 or bf16 (x_dtype), 1 <= M <= 16.
+ *                      fp32 accumulation, contraction split over waves and blocks, partials summed in a fixed order (no
+ *                      atomics: run-to-run bit-identical).  Workspace: oq_packed_gemv_workspace() bytes (0 = none needed).
+ *   oq_packed_gemm:    the same for any M (MFMA tile GEMM, fp32 epilogue: + bias + addend, one rounding to x_dtype).
+ *      Alignment: x and qweight 16 bytes, scales / y / addend 8 bytes. ------------------------------------------------ */
+int oq_packed_dequant(const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t in, int64_t out, int64_t group,
+                      int bits, void* w, int w_dtype, void* stream);
+int64_t oq_packed_gemv_workspace(int64_t M, int64_t in, int64_t out, int bits);
+int oq_packed_gemv(const void* x, int x_dtype, int64_t M, int64_t in, int64_t out, int64_t group, int bits,
+                   const int32_t* qweight, const int32_t* qzeros, const void* scales, const void* bias, const void* addend,
+                   void* y, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_packed_gemm(const void* x, int x_dtype, int64_t M, int64_t in, int64_t out, int64_t group, int bits,
+                   const int32_t* qweight, const int32_t* qzeros, const void* scales, const void* bias, const void* addend,
+                   void* y, void* stream);
+
 /* ---- fused causal attention (models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,

@@ -49,6 +49,32 @@ class QuantBlockMixin:
         from . import ops
         return hidden_states if back is None else ops.cast(hidden_states, back)
 
+    # ---- packed (real-quant) inference -----------------------------------------------------------------------------
+    # realquant.pack_block / load_packed_block mark the block; its forward checks the mark once at entry and runs a plain
+    # weight-only inference path on the PackedLinear kernels (no fake quant, no autograd, no graph capture).
+    def _packed_check(self, past_key_value=None, use_cache=False, output_attentions=False):
+        from ._capi import OQError
+        bits = self.__dict__["_oq_packed"]["act_bits"]
+        if bits < 16:
+            raise OQError(f"packed block with {bits}-bit activation quantisers: real quantisation is weight-only (AutoGPTQ's "
+                          "QuantLinear has no activation quantiser); evaluate W*A<16 models with the fake-quant block instead")
+        if past_key_value is not None or use_cache or output_attentions:
+            raise NotImplementedError("the packed inference path runs whole sequences, without KV cache / attention outputs")
+
+    @staticmethod
+    def _packed_attention(q, k, v, attention_mask, scale):
+        """softmax(scale * q k^T + mask) v on [bs, T, heads, hd] (k / v may have fewer heads: GQA): the fused causal kernel
+        where it covers the problem, else scores -> softmax -> PV on the HIP GEMM."""
+        from . import ops
+        bsz, T = q.shape[0], q.shape[1]
+        if attention_mask is not None and attention_mask.size() != (bsz, 1, T, T):
+            raise ValueError(f"Attention mask should be of size {(bsz, 1, T, T)}, but is {attention_mask.size()}")
+        causal = ops.mask_is_causal(attention_mask)
+        if ops.fused_attention_supported(q, causal):
+            return ops.FusedCausalAttnFn.apply(q, k, v, scale)
+        probs = ops.SoftmaxFn.apply(ops.AttnScoresFn.apply(q, k, causal), attention_mask, scale, causal)
+        return ops.AttnPVFn.apply(probs, v, causal)
+
     def _truncate_scales(self):
         arena = self.__dict__.get("_arena_truncate")
         if arena is not None:

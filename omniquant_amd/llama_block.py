@@ -283,6 +283,8 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
 
     def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None,
                 output_attentions=False, use_cache=False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        if self.__dict__.get("_oq_packed") is not None:
+            return self._packed_forward(hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache)
         hidden_states, back = self._enter(hidden_states)
         residual = hidden_states
         a = self.self_attn
@@ -312,3 +314,24 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
             h, res = self.post_attention_layernorm.forward_with_residual(hidden_states)   # residual-path grad joins in norm bwd
         hidden_states = self.mlp(h, residual=res, input_is_quantized=fq2 is not None, sib=sib2)
         return (self._leave(hidden_states, back),)
+
+    @torch.no_grad()
+    def _packed_forward(self, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache):
+        """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
+        in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual)."""
+        self._packed_check(past_key_value, use_cache, output_attentions)
+        x, back = self._enter(hidden_states)
+        a, m = self.self_attn, self.mlp
+        bsz, T, _ = x.shape
+        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+        h = self.input_layernorm(x)
+        q = a.q_proj(h).view(bsz, T, nh, hd)
+        k = a.k_proj(h).view(bsz, T, nkv, hd)
+        v = a.v_proj(h).view(bsz, T, nkv, hd)
+        cos, sin = a._rope_tables(position_ids, T, x.device)
+        q, k = ops.RopeFn.apply(q, cos, sin), ops.RopeFn.apply(k, cos, sin)
+        attn = self._packed_attention(q, k, v, attention_mask, 1.0 / math.sqrt(hd))
+        x = a.o_proj(attn.reshape(bsz, T, self.hidden_size), residual=x)
+        h = self.post_attention_layernorm(x)
+        x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
+        return (self._leave(x, back),)

@@ -94,6 +94,8 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
 
     def forward(self, hidden_states, attention_mask=None, layer_head_mask=None, output_attentions=False,
                 use_cache=False, past_key_value=None, **kwargs) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        if self.__dict__.get("_oq_packed") is not None:
+            return self._packed_forward(hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value)
         if use_cache or output_attentions:
             raise NotImplementedError("the calibration hot path runs without KV cache / attention outputs")
         hidden_states, back = self._enter(hidden_states)
@@ -130,3 +132,27 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         if not self.do_layer_norm_before:
             hidden_states = self.final_layer_norm(hidden_states)
         return (self._leave(hidden_states, back),)
+
+    @torch.no_grad()
+    def _packed_forward(self, hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value):
+        """Real-quant inference (realquant.pack_block): the same block with LayerNorm, biased PackedLinears and ReLU."""
+        self._packed_check(past_key_value, use_cache, output_attentions)
+        if layer_head_mask is not None:
+            raise NotImplementedError("the packed inference path runs without head masks")
+        x, back = self._enter(hidden_states)
+        a = self.self_attn
+        bsz, T, _ = x.shape
+        nh, hd = a.num_heads, a.head_dim
+        h = self.self_attn_layer_norm(x) if self.do_layer_norm_before else x
+        q = ops.ScaleFn.apply(a.q_proj(h), a.scaling).view(bsz, T, nh, hd)
+        k = a.k_proj(h).view(bsz, T, nh, hd)
+        v = a.v_proj(h).view(bsz, T, nh, hd)
+        attn = self._packed_attention(q, k, v, attention_mask, 1.0)
+        x = a.out_proj(attn.reshape(bsz, T, self.embed_dim), residual=x)
+        if not self.do_layer_norm_before:
+            x = self.self_attn_layer_norm(x)
+        h = self.final_layer_norm(x) if self.do_layer_norm_before else x
+        x = self.fc2(ops.ReluFn.apply(self.fc1(h)), residual=x)
+        if not self.do_layer_norm_before:
+            x = self.final_layer_norm(x)
+        return (self._leave(x, back),)

@@ -1,13 +1,24 @@
-"""Real-quant packing on the HIP path (`--real_quant`, quantize/omniquant.py:255-278).
+"""Real-quant packing and inference on the HIP path (`--real_quant`, quantize/omniquant.py:255-278; main.py:364 evaluates
+the packed model).
 
 The reference hands every folded QuantLinear to AutoGPTQ's `qlinear_cuda.QuantLinear.pack` (third-party, not vendored:
 PARITY UNPINNED, see csrc/oq_pack.hip).  `pack_linear` produces the same buffers (`qweight`, `qzeros`, `scales`, `g_idx`,
-`bias`, AutoGPTQ names and shapes) with one HIP kernel; `PackedLinear` is a minimal container with a `dequantize()`
-that inverts the packing (used by the tests' round trip; inference kernels are out of scope)."""
+`bias`, AutoGPTQ names and shapes) with one HIP kernel.  `PackedLinear` runs straight from them (csrc/oq_packed.hip):
+`oq_packed_gemv` for skinny inputs (decode), `oq_packed_gemm` above the row threshold (prefill), and for float32
+activations `oq_packed_dequant` + the exact-f32 `oq_gemm`.  `dequantize()` (pure torch) is the value contract the kernels
+reproduce.  `pack_block` / `load_packed_block` turn a decoder block into its packed form, whose forward then takes the
+weight-only inference path of llama_block.py / opt_block.py."""
+import os
+
 import torch
 import torch.nn as nn
 
 from . import _capi as C
+
+#: rows up to which PackedLinear takes oq_packed_gemv (set by tools/microbench_packed.py)
+GEMV_MAX_ROWS = int(os.environ.get("OQ_PACKED_GEMV_ROWS", "16"))
+#: bf16 prefill through oq_packed_dequant + oq_gemm instead of oq_packed_gemm (the faster of the two at M = 2048, measured)
+PREFILL_BF16_DEQUANT = os.environ.get("OQ_PACKED_PREFILL_DEQUANT", "1") != "0"
 
 
 def pack_linear(weight, scales, zeros, bits, group_size=None, bias=None):
@@ -54,14 +65,49 @@ def unpack(q, bits, n):
 
 
 class PackedLinear(nn.Module):
+    """AutoGPTQ-layout linear (buffers qweight / qzeros / scales / g_idx / bias, AutoGPTQ's names, shapes and dtypes).
+
+    forward(x, residual=None) = x @ W^T (+ bias) (+ residual), W = dequantize() -- fp16 x: exactly that weight; bf16 x: that
+    weight rounded to bf16 (the bf16 MFMA operand); float32 x: the fp16 weight widened exactly, contracted
+    in exact f32.  Inference only: the packed weights have no gradient and no gradient is propagated to x either (a call
+    that would need one raises OQError; a calibrated block is trained before packing, never after)."""
+
     def __init__(self, bits, group_size, in_features, out_features, packed):
         super().__init__()
         self.bits, self.group_size, self.infeatures, self.outfeatures = bits, group_size or in_features, in_features, out_features
+        _check_shape(bits, self.group_size, in_features, out_features)
         for k, v in packed.items():
             if v is not None:
                 self.register_buffer(k, v)
             else:
                 setattr(self, k, None)
+        self._check_g_idx()
+
+    @classmethod
+    def empty(cls, bits, group_size, in_features, out_features, bias, device):
+        """Buffers of the right shapes / dtypes (uninitialised, g_idx = the trivial grouping) that a saved state_dict() of a
+        PackedLinear loads into.  bias: True / False (or a tensor / None)."""
+        group = group_size or in_features
+        _check_shape(bits, group, in_features, out_features)
+        packed = dict(qweight=torch.zeros((in_features // 32 * bits, out_features), dtype=torch.int32, device=device),
+                      qzeros=torch.zeros((in_features // group, out_features // 32 * bits), dtype=torch.int32, device=device),
+                      scales=torch.zeros((in_features // group, out_features), dtype=torch.float16, device=device),
+                      g_idx=torch.arange(in_features, dtype=torch.int32, device=device) // group,
+                      bias=torch.zeros((out_features,), dtype=torch.float16, device=device) if bias is not None and bias is not False
+                      else None)
+        return cls(bits, group, in_features, out_features, packed)
+
+    def _check_g_idx(self):
+        """Only the trivial grouping g_idx = arange(in) // group: act-order (a permuted g_idx) has no kernel.  Checked when the
+        buffers are set (construction, load_state_dict), never per call."""
+        g = self.g_idx
+        want = torch.arange(self.infeatures, device=g.device, dtype=torch.int64) // self.group_size
+        if tuple(g.shape) != (self.infeatures,) or not torch.equal(g.long(), want):
+            raise C.OQError("PackedLinear: g_idx is not arange(in) // group_size (act-order / desc_act is not supported)")
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._check_g_idx()
 
     def dequantize(self):
         """fp16 weight [out, in] = scales * (q - (qzeros + 1))  (AutoGPTQ's dequantisation)."""
@@ -71,10 +117,84 @@ class PackedLinear(nn.Module):
         w = self.scales.float()[g] * (q - z[g]).float()
         return w.t().contiguous().half()
 
+    def dequantize_hip(self, dtype=torch.float16):
+        """dequantize() on the GPU (oq_packed_dequant), in float16 (bit-exact), bfloat16 or float32."""
+        if not self.qweight.is_cuda:
+            raise C.OQError("PackedLinear: GPU buffers expected (no CPU fallback)")
+        w = torch.empty((self.outfeatures, self.infeatures), dtype=dtype, device=self.qweight.device)
+        C.call("oq_packed_dequant", C.ptr(self.qweight), C.ptr(self.qzeros), C.ptr(self.scales), self.infeatures,
+               self.outfeatures, self.group_size, self.bits, C.ptr(w), C.dt(w), C.stream())
+        return w
+
+    def forward(self, x, residual=None):
+        if not x.is_cuda or not self.qweight.is_cuda:
+            raise C.OQError("PackedLinear: the HIP path needs GPU tensors (got a CPU tensor); there is no CPU fallback")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise C.OQError("PackedLinear is inference-only: no gradient through a packed weight (run under torch.no_grad())")
+        if x.shape[-1] != self.infeatures:
+            raise C.OQError(f"PackedLinear: input has {x.shape[-1]} features, the layer {self.infeatures}")
+        if x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise C.OQError(f"PackedLinear: activation dtype {x.dtype} (float16, bfloat16 or float32)")
+        K, N = self.infeatures, self.outfeatures
+        x2 = x.reshape(-1, K).contiguous()
+        M = x2.shape[0]
+        res2 = None
+        if residual is not None:
+            if residual.dtype != x.dtype or residual.numel() != M * N:
+                raise C.OQError("PackedLinear: residual must have the output's dtype and size")
+            res2 = residual.reshape(M, N).contiguous()
+        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        if M == 0:
+            return y.view(*x.shape[:-1], N)
+        from . import ops
+        if x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and M > GEMV_MAX_ROWS and PREFILL_BF16_DEQUANT):
+            # dequantise once into a dense temporary, then the resident-weight GEMM (exact f32 MFMA in parity mode)
+            w = self.dequantize_hip(x.dtype)
+            b32 = None if self.bias is None else self.bias.float().contiguous()
+            ops.gemm(x2, w, y, M, N, K, K, K, N, True, True, bias=b32, addend=res2)
+        elif M <= GEMV_MAX_ROWS:
+            ws_n = C.size_call("oq_packed_gemv_workspace", M, K, N, self.bits)
+            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device) if ws_n else None
+            C.call("oq_packed_gemv", C.ptr(x2), C.dt(x2), M, K, N, self.group_size, self.bits, C.ptr(self.qweight),
+                   C.ptr(self.qzeros), C.ptr(self.scales), C.ptr(self.bias), C.ptr(res2), C.ptr(y), C.ptr(ws), ws_n, C.stream())
+        else:
+            C.call("oq_packed_gemm", C.ptr(x2), C.dt(x2), M, K, N, self.group_size, self.bits, C.ptr(self.qweight),
+                   C.ptr(self.qzeros), C.ptr(self.scales), C.ptr(self.bias), C.ptr(res2), C.ptr(y), C.stream())
+        return y.view(*x.shape[:-1], N)
+
+
+def _check_shape(bits, group, inn, out):
+    if bits not in (2, 3, 4, 8):
+        raise C.OQError(f"PackedLinear: bits {bits} (2, 3, 4 or 8)")
+    if inn <= 0 or out <= 0 or inn % 32 or out % 32:
+        raise C.OQError(f"PackedLinear: in={inn} out={out} (multiples of 32)")
+    if group <= 0 or inn % group or (group != inn and group % 32):
+        raise C.OQError(f"PackedLinear: group {group} (in={inn}, or a divisor of it that is a multiple of 32)")
+
+
+def _act_bits(qlayer):
+    """Smallest activation bit width the block's quantisers were built with (16 = none acts: weight-only)."""
+    from .linear import QuantLinear
+    from .matmul import QuantMatMul
+    bits = [16]
+    for m in qlayer.modules():
+        if isinstance(m, QuantLinear) and m.act_quantizer is not None and not m.disable_input_quant:
+            bits.append(m.act_quantizer.n_bits)
+        elif isinstance(m, QuantMatMul):
+            bits += [m.x1_quantizer.n_bits, m.x2_quantizer.n_bits]
+    return min(bits)
+
+
+def _mark_packed(qlayer, act_bits):
+    """The block's forward checks this once at entry and takes the packed inference path (block_common.packed_guard)."""
+    qlayer._oq_packed = {"act_bits": int(act_bits)}
+
 
 def pack_block(qlayer, wbits):
-    """Replace every folded QuantLinear of a calibrated block by a PackedLinear (quantize/omniquant.py:255-278)."""
+    """Replace every folded QuantLinear of a calibrated block by a PackedLinear (quantize/omniquant.py:255-278) and mark the
+    block packed: its forward then runs the weight-only inference path."""
     from .linear import QuantLinear
+    act_bits = _act_bits(qlayer)
     for name, module in list(qlayer.named_modules()):
         if not isinstance(module, QuantLinear):
             continue
@@ -86,4 +206,33 @@ def pack_block(qlayer, wbits):
         for p_ in parts[:-1]:
             parent = getattr(parent, p_)
         setattr(parent, parts[-1], pl)
+    _mark_packed(qlayer, act_bits)
+    return qlayer
+
+
+def load_packed_block(qlayer, state_dict, wbits, group_size):
+    """Turn a fresh Quant*DecoderLayer (built from the model's layer and the run's args, not calibrated) into the packed block
+    whose state_dict() this is, without recalibrating: every QuantLinear becomes an empty PackedLinear, the LET-folded norm
+    biases get their buffers, then the state dict is loaded (float LET / LWC learnables it still holds are not needed for
+    inference and are ignored; any missing tensor is an error)."""
+    from .linear import QuantLinear
+    from .norm import OmniLayerNorm, OmniLlamaRMSNorm
+    act_bits = _act_bits(qlayer)
+    for name, module in list(qlayer.named_modules()):
+        if isinstance(module, QuantLinear):
+            pl = PackedLinear.empty(wbits, group_size, module.in_features, module.out_features, (name + ".bias") in state_dict,
+                                    module.weight.device)
+            parent = qlayer
+            parts = name.split(".")
+            for p_ in parts[:-1]:
+                parent = getattr(parent, p_)
+            setattr(parent, parts[-1], pl)
+        elif isinstance(module, (OmniLayerNorm, OmniLlamaRMSNorm)) and module.bias is None and (name + ".bias") in state_dict:
+            ref = state_dict[name + ".bias"]
+            del module.bias
+            module.register_buffer("bias", torch.empty(ref.shape, dtype=ref.dtype, device=module.weight.device))
+    missing, _ = qlayer.load_state_dict(state_dict, strict=False)
+    if missing:
+        raise C.OQError(f"load_packed_block: the state dict lacks {missing}")
+    _mark_packed(qlayer, act_bits)
     return qlayer
