@@ -309,6 +309,29 @@ int oq_packed_gemm(const void* x, int x_dtype, int64_t M, int64_t in, int64_t ou
                    const int32_t* qweight, const int32_t* qzeros, const void* scales, const void* bias, const void* addend,
                    void* y, void* stream);
 
+/* ---- incremental decoding of the packed blocks (models/int_llama_layer.py:121-135,143-163,177 and
+ *      models/int_opt_layer.py:110-121: rotary embedding at position_ids, torch.cat with past_key_value, attention of the new
+ *      queries against the whole cache).  The cache is [bs, nkv, cap, hd] (rows [0, L) valid), dtype OQ_BF16 or OQ_F32.
+ *   oq_kv_append: q [bs,Tq,nh,hd] (may be NULL with nh = 0), k / v [bs,Tq,nkv,hd] (the projections' outputs).  Writes the
+ *      rotated q to q_out (may alias q), the rotated k to cache rows [past, past+Tq) (and to k_out [bs,Tq,nkv,hd] if not NULL),
+ *      v unrotated to the v cache.  cos / sin f32 [P, hd] tables over positions 0..P-1, row p = what oq_rope is given for
+ *      position p; the rotation is oq_rope's arithmetic bit for bit.  cos == NULL: no rotation (OPT).  pos int64
+ *      [bs or 1, Tq] at pos + b * pos_bstride + t (pos_bstride 0 = one row for the batch); NULL = past + t.  Positions outside
+ *      [0, P) are CLAMPED to the table (never read out of bounds); callers size P >= past + Tq.
+ *   oq_attn_decode: o [bs,Tq,nh,hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over cache rows j < L (L = past + Tq,
+ *      Tq <= L <= cap; rows >= L are never read), query head h reading kv head h / (nh / nkv).  fp32 online softmax, one
+ *      rounding of o.  mask: NULL, or additive [bs or 1, 1, Tq, L] in mask_dtype (f32 / fp16 / bf16), element
+ *      mask[b * mask_bstride + t * mask_ld + j] (mask_bstride 0 = broadcast over the batch).  hd 64 or 128.  The L rows are
+ *      split into a number of chunks that depends on (bs, nkv, L) only: results are bit-reproducible and independent of cap.
+ *      workspace: oq_attn_decode_workspace() bytes (fp32 partials, combined in split order by a second launch). */
+int oq_kv_append(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache, int dtype,
+                 int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past, const float* cos, const float* sin,
+                 int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream);
+int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd);
+int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
+                   int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
+                   int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused causal attention (models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,

@@ -69,6 +69,10 @@ SIGNATURES = {
     "oq_packed_dequant": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _vp],
     "oq_packed_gemv": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "oq_packed_gemm": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "oq_kv_append": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _i64,
+                     _vp],
+    "oq_attn_decode": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _i32, _i64, _i64, _vp, _i64,
+                       _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,
@@ -108,7 +112,8 @@ SIZE_FUNCS = {"oq_fakequant_bwd_workspace": [_i64, _i64], "oq_norm_bwd_workspace
               "oq_attn_supported": [_i32, _i64, _i32, _i32], "oq_wgrad_group_workspace": [_vp, _i32], "oq_act_stats_workspace": [_i64, _i64],
               "oq_colsum_workspace": [_i64, _i64], "oq_gemm_workspace": [_i64, _i64, _i64, _i32, _i64, _i32], "oq_rope_quant_supported": [_i32, _i32],
               "oq_norm_quant_supported": [_i32, _i64], "oq_norm_quant_bwd_workspace": [_i64, _i64],
-              "oq_fakequant_codes_supported": [_i64, _i64, _i32, _i32], "oq_packed_gemv_workspace": [_i64, _i64, _i64, _i32]}
+              "oq_fakequant_codes_supported": [_i64, _i64, _i32, _i32], "oq_packed_gemv_workspace": [_i64, _i64, _i64, _i32],
+              "oq_attn_decode_workspace": [_i64, _i32, _i32, _i64, _i64, _i32]}
 
 _lib = None
 

@@ -58,8 +58,55 @@ class QuantBlockMixin:
         if bits < 16:
             raise OQError(f"packed block with {bits}-bit activation quantisers: real quantisation is weight-only (AutoGPTQ's "
                           "QuantLinear has no activation quantiser); evaluate W*A<16 models with the fake-quant block instead")
-        if past_key_value is not None or use_cache or output_attentions:
-            raise NotImplementedError("the packed inference path runs whole sequences, without KV cache / attention outputs")
+        if output_attentions:
+            raise NotImplementedError("the packed inference path does not return attention weights")
+
+    # ---- incremental decoding (past_key_value / use_cache) on the packed path ----------------------------------------------
+    def _kv_cache_in(self, past_key_value, bsz, Tq, nkv, hd, x):
+        """The PackedKVCache this forward appends to: a new one (prefill), the caller's (appended in place) or a copy of a
+        reference-layout (k, v) tuple converted to the compute dtype (the caller's tensors are left alone)."""
+        from ._capi import OQError
+        from .kvcache import PackedKVCache
+        if hd not in (64, 128):
+            raise OQError(f"KV-cache decoding covers head_dim 64 and 128 (oq_attn_decode), not {hd}")
+        if past_key_value is None:
+            return PackedKVCache(bsz, nkv, hd, x.dtype, x.device, Tq)
+        if isinstance(past_key_value, PackedKVCache):
+            c = past_key_value
+            if (c.bs, c.nkv, c.hd) != (bsz, nkv, hd) or c.dtype != x.dtype or c.device != x.device:
+                raise OQError(f"{c!r} does not fit this block's step: batch {bsz}, {nkv} kv heads of {hd}, {x.dtype} on {x.device}")
+            return c
+        if isinstance(past_key_value, (tuple, list)) and len(past_key_value) == 2:
+            k = past_key_value[0]
+            if not torch.is_tensor(k) or k.dim() != 4 or (k.shape[0], k.shape[1], k.shape[3]) != (bsz, nkv, hd):
+                raise OQError(f"past_key_value {tuple(getattr(k, 'shape', ()))}: expected [{bsz}, {nkv}, T, {hd}]")
+            return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq)
+        raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
+
+    def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None):
+        """Attention of this step's q [bs, Tq, nh, hd] over the cache plus this step's k / v, which are appended to it (rotated
+        by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
+        (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation."""
+        from . import ops
+        bsz, Tq = q.shape[0], q.shape[1]
+        past = cache.length
+        L = past + Tq
+        if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[0] not in (1, bsz)
+                                           or tuple(attention_mask.shape[1:]) != (1, Tq, L)):
+            raise ValueError(f"Attention mask should be of size {(bsz, 1, Tq, L)}, but is {attention_mask.size()}")
+        cache.reserve(Tq)
+        rot = cos is not None
+        qr = torch.empty_like(q) if rot else q
+        kr = torch.empty_like(k) if (rot and past == 0) else None
+        ops.kv_append(k, v, cache.k, cache.v, past, q=q if rot else None, q_out=qr if rot else None, k_out=kr, cos=cos, sin=sin,
+                      positions=positions)
+        cache.length = L
+        if past == 0:
+            mask = attention_mask
+            if mask is not None and mask.shape[0] != bsz:
+                mask = mask.expand(bsz, 1, Tq, L)
+            return self._packed_attention(qr, kr if rot else k, v, mask, scale)
+        return ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
 
     @staticmethod
     def _packed_attention(q, k, v, attention_mask, scale):

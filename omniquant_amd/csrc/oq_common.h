@@ -202,5 +202,18 @@ __device__ __forceinline__ float vmin3(float a, float b, float c) {
     return r;
 }
 
+// RoPE forward on one 8-element slice of each half of a head: x*cos + rotate_half(x)*sin, rotate_half(x) = cat(-x2, x1);
+// a / b are x1 / x2, c1 / s1 and c2 / s2 the table entries of the same columns.  The one expression order shared by every
+// kernel that rotates (oq_rope, oq_kv_append), so that they agree bit for bit (all built with -ffp-contract=off).
+__device__ __forceinline__ void oq_rope_fwd8(const float (&a)[8], const float (&b)[8], const float (&c1)[8],
+                                             const float (&s1)[8], const float (&c2)[8], const float (&s2)[8],
+                                             float (&oa)[8], float (&ob)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        oa[i] = a[i] * c1[i] + (-b[i]) * s1[i];
+        ob[i] = b[i] * c2[i] + a[i] * s2[i];
+    }
+}
+
 static inline int oq_dtype_size(int dt) { return dt == OQ_F32 ? 4 : 2; }
 static inline bool oq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -1,0 +1,358 @@
+// Incremental-decoding kernels of the packed (real-quant) blocks on gfx950: the KV-cache append with RoPE at arbitrary
+// positions, and attention of 1..Tq query rows against the cached K/V.
+// Reference lines: models/int_llama_layer.py:121-135,177 (rotary embedding gathered at position_ids, torch.cat with
+// past_key_value, present_key_value) and :143-163 (scores, mask, softmax, PV); models/int_opt_layer.py:110-121,151-170.
+//
+// Decode attention is HBM-bound streaming: few query rows meet a long K/V.  One workgroup per (batch, kv head, split of
+// the L cached rows) serves every query row that reads that kv head (rep = nh / nkv query heads times Tq queries), so each
+// K/V byte leaves HBM once per step.  Each key row is read by hd/8 lanes with 16-byte loads straight into VGPRs; scores are
+// reduced across those lanes with DPP, the softmax is online (fp32, exp2 with log2(e) folded in), and each split writes its
+// (max, sum, accumulator) partials to a workspace that a second launch combines in split order.  No atomics: for one
+// problem the bits do not change from launch to launch, nor with the cache capacity.
+#include "oq_common.h"
+
+namespace {
+
+// ---- KV append: q [bs,Tq,nh,hd], k / v [bs,Tq,nkv,hd] -> rotated q (q_out), rotated k (cache rows past.., and k_out),
+//      plain v (cache).  One work item = 8 elements of a head's first half and the 8 partners of its second half. -------------
+template <typename T>
+__global__ void __launch_bounds__(256) kv_append_kernel(const T* q, const T* k, const T* v, T* q_out, T* k_out, T* kc, T* vc,
+                                                        int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                                                        int64_t past, const float* cs, const float* sn, int64_t P,
+                                                        const int64_t* pos, int64_t pos_bs) {
+    const int half = hd / 2, hv = hd / 16;
+    const int nslot = nh + 2 * nkv;
+    const int64_t n = bs * Tq * nslot * hv;
+    for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) {
+        const int d0 = (int)(it % hv) * 8;
+        int64_t r = it / hv;
+        const int slot = (int)(r % nslot);
+        r /= nslot;
+        const int64_t t = r % Tq, b = r / Tq;
+        const T* src;
+        T* dst;
+        T* dst2 = nullptr;
+        bool rot = cs != nullptr;
+        if (slot < nh) {
+            src = q + ((b * Tq + t) * nh + slot) * hd;
+            dst = q_out + ((b * Tq + t) * nh + slot) * hd;
+        } else if (slot < nh + nkv) {
+            const int h = slot - nh;
+            src = k + ((b * Tq + t) * nkv + h) * hd;
+            dst = kc + ((b * nkv + h) * cap + past + t) * hd;
+            if (k_out) dst2 = k_out + ((b * Tq + t) * nkv + h) * hd;
+        } else {
+            const int h = slot - nh - nkv;
+            src = v + ((b * Tq + t) * nkv + h) * hd;
+            dst = vc + ((b * nkv + h) * cap + past + t) * hd;
+            rot = false;
+        }
+        float a[8], c[8];
+        Vec8<T>::load(src + d0, a);
+        Vec8<T>::load(src + half + d0, c);
+        if (rot) {
+            // positions outside [0, P) are clamped to the table, never read out of bounds (the host sizes P >= past + Tq)
+            int64_t p = pos ? pos[b * pos_bs + t] : past + t;
+            p = p < 0 ? 0 : (p >= P ? P - 1 : p);
+            float c1[8], s1[8], c2[8], s2[8], oa[8], ob[8];
+            Vec8<float>::load(cs + p * hd + d0, c1);
+            Vec8<float>::load(sn + p * hd + d0, s1);
+            Vec8<float>::load(cs + p * hd + half + d0, c2);
+            Vec8<float>::load(sn + p * hd + half + d0, s2);
+            oq_rope_fwd8(a, c, c1, s1, c2, s2, oa, ob);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { a[i] = oa[i]; c[i] = ob[i]; }
+        }
+        Vec8<T>::store(dst + d0, a);
+        Vec8<T>::store(dst + half + d0, c);
+        if (dst2) {
+            Vec8<T>::store(dst2 + d0, a);
+            Vec8<T>::store(dst2 + half + d0, c);
+        }
+    }
+}
+
+// ---- decode attention ----------------------------------------------------------------------------------------------------
+constexpr int DEC_THREADS = 256;
+constexpr int DEC_TARGET_WG = 1024;     // 4 workgroups of 4 waves per CU
+constexpr int DEC_MAX_SPLIT = 64;
+constexpr int DEC_MIN_KEYS = 128;       // a split covers at least this many cached rows (L <= 128: one split)
+
+// The split count depends on the problem shape only (never on cap or on the data): results are reproducible bit for bit.
+inline int dec_splits(int64_t bs, int64_t nkv, int64_t L) {
+    int64_t ns = (DEC_TARGET_WG + bs * nkv - 1) / (bs * nkv);
+    if (ns > DEC_MAX_SPLIT) ns = DEC_MAX_SPLIT;
+    const int64_t by_len = (L + DEC_MIN_KEYS - 1) / DEC_MIN_KEYS;
+    if (ns > by_len) ns = by_len;
+    return ns < 1 ? 1 : (int)ns;
+}
+
+inline int dec_qb(int64_t R) { return R >= 8 ? 8 : (R >= 3 ? 4 : (R == 2 ? 2 : 1)); }
+
+__device__ __forceinline__ float ld_mask(const void* m, int mdt, int64_t i) {
+    if (mdt == OQ_F32) return reinterpret_cast<const float*>(m)[i];
+    if (mdt == OQ_BF16) return (float)reinterpret_cast<const bf16_t*>(m)[i];
+    return (float)reinterpret_cast<const f16_t*>(m)[i];
+}
+
+// Split kernel: grid (ns, nkv, bs).  Lane group `grp` (hd/8 lanes) handles rows j0 + grp, j0 + grp + G, ... of the split,
+// U rows in flight; query rows are processed QB at a time (rows r = t*rep + i of this kv head).  Workspace per
+// (b, kv head, split, r): [m, l, acc[HD]] with m in the log2 domain.
+template <typename T, int HD, int QB>
+__global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, const T* kc, const T* vc, float* ws, int64_t Tq,
+                                                                  int nh, int nkv, int64_t cap, int64_t L, float scale,
+                                                                  const void* mask, int mdt, int64_t m_bs, int64_t m_ld, int ns) {
+    constexpr int LPK = HD / 8;
+    constexpr int GPW = 64 / LPK;
+    constexpr int G = GPW * (DEC_THREADS / 64);
+    constexpr int U = QB >= 8 ? 2 : 4;
+    const float log2e = 1.4426950408889634f, lowest = -3.4028234663852886e38f;
+    __shared__ float red_m[G], red_l[G];
+    __shared__ float red_acc[G][HD];
+
+    const int split = blockIdx.x, kvh = blockIdx.y;
+    const int64_t b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int grp = (tid >> 6) * GPW + lane / LPK, d0 = (lane % LPK) * 8;
+    const int rep = nh / nkv;
+    const int64_t R = (int64_t)rep * Tq;
+    const int64_t chunk = (L + ns - 1) / ns;
+    const int64_t j0 = split * chunk, j1 = (j0 + chunk < L) ? j0 + chunk : L;
+    const T* kb = kc + (b * nkv + kvh) * cap * HD + d0;
+    const T* vb = vc + (b * nkv + kvh) * cap * HD + d0;
+    float* wsb = ws + ((b * nkv + kvh) * ns + split) * R * (HD + 2);
+    const float zs = scale * log2e;
+
+    for (int64_t r0 = 0; r0 < R; r0 += QB) {
+        float qv[QB][8], m[QB], l[QB], acc[QB][8];
+        int64_t moff[QB];
+#pragma unroll
+        for (int rr = 0; rr < QB; ++rr) {
+            const int64_t r = r0 + rr < R ? r0 + rr : R - 1;        // padding rows repeat the last one (never stored)
+            const int64_t t = r / rep;
+            Vec8<T>::load(q + ((b * Tq + t) * nh + (int64_t)kvh * rep + (r % rep)) * HD + d0, qv[rr]);
+            moff[rr] = b * m_bs + t * m_ld;
+            m[rr] = -INFINITY;
+            l[rr] = 0.f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[rr][i] = 0.f;
+        }
+        // the trip count is uniform over the workgroup; rows past j1 are masked per lane group (and never loaded)
+        for (int64_t jb = j0; jb < j1; jb += (int64_t)G * U) {
+            Raw8<T> kr[U], vr[U];
+            bool ok[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t j = jb + u * G + grp;
+                ok[u] = j < j1;
+                if (ok[u]) {
+                    kr[u].load(kb + j * HD);
+                    vr[u].load(vb + j * HD);
+                }
+            }
+            float z[U][QB];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float kf[8];
+                if (ok[u]) kr[u].unpack(kf);
+                else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) kf[i] = 0.f;
+                }
+                const int64_t j = jb + u * G + grp;
+#pragma unroll
+                for (int rr = 0; rr < QB; ++rr) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) s = __builtin_fmaf(qv[rr][i], kf[i], s);
+                    s = wave_sum(s, LPK);                       // every lane of the group holds q . k_j
+                    float zz;
+                    if (mask) {
+                        const float mv = ok[u] ? ld_mask(mask, mdt, moff[rr] + j) : 0.f;
+                        zz = fmaxf((s * scale + mv) * log2e, lowest);   // max(z, -FLT_MAX) as oq_softmax_fwd, in log2 units
+                    } else {
+                        zz = s * zs;
+                    }
+                    z[u][rr] = ok[u] ? zz : -INFINITY;
+                }
+            }
+#pragma unroll
+            for (int rr = 0; rr < QB; ++rr) {
+                float mx = m[rr];
+#pragma unroll
+                for (int u = 0; u < U; ++u) mx = fmaxf(mx, z[u][rr]);
+                // (a lane group with no row yet keeps m = -inf: no rescale)
+                const float c = mx == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m[rr] - mx);
+                m[rr] = mx;
+                l[rr] *= c;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc[rr][i] *= c;
+#pragma unroll
+                for (int u = 0; u < U; ++u) z[u][rr] = ok[u] ? __builtin_amdgcn_exp2f(z[u][rr] - mx) : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float vf[8];
+                if (ok[u]) vr[u].unpack(vf);
+                else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) vf[i] = 0.f;
+                }
+#pragma unroll
+                for (int rr = 0; rr < QB; ++rr) {
+                    l[rr] += z[u][rr];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) acc[rr][i] = __builtin_fmaf(z[u][rr], vf[i], acc[rr][i]);
+                }
+            }
+        }
+        // combine the G lane groups of the workgroup in group order, one query row at a time
+#pragma unroll
+        for (int rr = 0; rr < QB; ++rr) {
+            const int64_t r = r0 + rr;
+            if (r >= R) break;                                       // uniform over the workgroup
+            if (lane % LPK == 0) red_m[grp] = m[rr];
+            __syncthreads();
+            float M = -INFINITY;
+            for (int g = 0; g < G; ++g) M = fmaxf(M, red_m[g]);
+            const float w = m[rr] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[rr] - M);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) red_acc[grp][d0 + i] = acc[rr][i] * w;
+            if (lane % LPK == 0) red_l[grp] = l[rr] * w;
+            __syncthreads();
+            float* wr = wsb + r * (HD + 2);
+            if (tid < HD) {
+                float s = 0.f;
+                for (int g = 0; g < G; ++g) s += red_acc[g][tid];
+                wr[2 + tid] = s;
+            } else if (tid == HD) {
+                float s = 0.f;
+                for (int g = 0; g < G; ++g) s += red_l[g];
+                wr[0] = M;
+                wr[1] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Combine kernel: one workgroup of HD threads per (b, kv head, r); splits merged in split order, one rounding to T.
+template <typename T, int HD>
+__global__ void __launch_bounds__(HD) attn_decode_combine_kernel(const float* ws, T* o, int64_t Tq, int nh, int nkv, int ns) {
+    const int rep = nh / nkv;
+    const int64_t R = (int64_t)rep * Tq;
+    const int64_t row = blockIdx.x;
+    const int64_t r = row % R, bk = row / R;
+    const int64_t kvh = bk % nkv, b = bk / nkv;
+    const int tid = threadIdx.x;
+    const float* w = ws + (bk * ns * R + r) * (HD + 2);
+    const int64_t st = R * (HD + 2);
+    float M = -INFINITY;
+    for (int s = 0; s < ns; ++s) M = fmaxf(M, w[s * st]);
+    float l = 0.f, a = 0.f;
+    for (int s = 0; s < ns; ++s) {
+        const float ms = w[s * st];
+        const float f = ms == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ms - M);
+        l += f * w[s * st + 1];
+        a += f * w[s * st + 2 + tid];
+    }
+    const int64_t t = r / rep;
+    st1(o + ((b * Tq + t) * nh + kvh * rep + (r % rep)) * HD + tid, a / l);
+}
+
+template <typename T, int HD, int QB>
+void launch_decode(const void* q, const void* kc, const void* vc, void* o, float* ws, int64_t bs, int64_t Tq, int nh, int nkv,
+                   int64_t cap, int64_t L, float scale, const void* mask, int mdt, int64_t m_bs, int64_t m_ld, int ns,
+                   hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB>), dim3(ns, nkv, bs), dim3(DEC_THREADS), 0, st, (const T*)q, (const T*)kc,
+                       (const T*)vc, ws, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns);
+    const int64_t rows = bs * (int64_t)nh * Tq;
+    hipLaunchKernelGGL((attn_decode_combine_kernel<T, HD>), dim3(rows), dim3(HD), 0, st, (const float*)ws, (T*)o, Tq, nh, nkv, ns);
+}
+
+template <typename T, int HD>
+void launch_decode_qb(int qb, const void* q, const void* kc, const void* vc, void* o, float* ws, int64_t bs, int64_t Tq, int nh,
+                      int nkv, int64_t cap, int64_t L, float scale, const void* mask, int mdt, int64_t m_bs, int64_t m_ld,
+                      int ns, hipStream_t st) {
+    switch (qb) {
+        case 1: launch_decode<T, HD, 1>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
+        case 2: launch_decode<T, HD, 2>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
+        case 4: launch_decode<T, HD, 4>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
+        default: launch_decode<T, HD, 8>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
+    }
+}
+
+}  // namespace
+
+extern "C" int oq_kv_append(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
+                            int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
+                            const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                            void* stream) {
+    OQ_CHECK_ARG(k && v && k_cache && v_cache, "oq_kv_append: null pointer");
+    OQ_CHECK_ARG(!q || q_out, "oq_kv_append: q without q_out");
+    OQ_CHECK_ARG(bs > 0 && Tq > 0 && nkv > 0 && nh >= 0 && (q || nh == 0), "oq_kv_append: bad shape");
+    OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "oq_kv_append: head_dim %d must be a multiple of 16", hd);
+    OQ_CHECK_ARG(past >= 0 && past + Tq <= cap, "oq_kv_append: rows [%lld, %lld) exceed the capacity %lld", (long long)past,
+                 (long long)(past + Tq), (long long)cap);
+    OQ_CHECK_ARG(!cos == !sin, "oq_kv_append: cos and sin go together");
+    OQ_CHECK_ARG(!cos || (P > 0 && oq_aligned16(cos) && oq_aligned16(sin)), "oq_kv_append: cos/sin tables must be 16-byte aligned, P > 0");
+    OQ_CHECK_ARG(pos_bstride >= 0, "oq_kv_append: pos_bstride");
+    const void* ptrs[] = {q, k, v, q_out, k_out, k_cache, v_cache};
+    for (const void* p : ptrs) OQ_CHECK_ARG(!p || oq_aligned16(p), "oq_kv_append: tensors must be 16-byte aligned");
+    const int64_t n = bs * Tq * (nh + 2 * nkv) * (hd / 16);
+    const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == OQ_F32) {
+        hipLaunchKernelGGL((kv_append_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v,
+                           (float*)q_out, (float*)k_out, (float*)k_cache, (float*)v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin,
+                           P, pos, pos_bstride);
+    } else if (dtype == OQ_BF16) {
+        hipLaunchKernelGGL((kv_append_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+                           (const bf16_t*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)k_cache, (bf16_t*)v_cache, bs, Tq, nh, nkv, hd,
+                           cap, past, cos, sin, P, pos, pos_bstride);
+    } else {
+        oq_set_error("oq_kv_append: dtype %d unsupported", dtype);
+        return OQ_E_UNSUPPORTED;
+    }
+    OQ_CHECK_LAUNCH("oq_kv_append");
+    return OQ_OK;
+}
+
+extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd) {
+    if (bs <= 0 || nkv <= 0 || nh <= 0 || nh % nkv || Tq <= 0 || L <= 0 || hd <= 0) return 0;
+    return (int64_t)dec_splits(bs, nkv, L) * bs * nh * Tq * (hd + 2) * (int64_t)sizeof(float);
+}
+
+extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq,
+                              int nh, int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype,
+                              int64_t mask_bstride, int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
+    OQ_CHECK_ARG(q && k_cache && v_cache && o && workspace, "oq_attn_decode: null pointer");
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_attn_decode: head_dim %d (64 or 128)", hd);
+    OQ_CHECK_ARG(bs > 0 && bs <= 65535 && nkv > 0 && nkv <= 65535 && nh > 0 && nh % nkv == 0,
+                 "oq_attn_decode: bad heads %d / %d or batch %lld", nh, nkv, (long long)bs);
+    OQ_CHECK_ARG(Tq > 0 && L >= Tq && L <= cap, "oq_attn_decode: need 1 <= Tq (%lld) <= L (%lld) <= cap (%lld)", (long long)Tq,
+                 (long long)L, (long long)cap);
+    OQ_CHECK_ARG(!mask || mask_dtype == OQ_F32 || mask_dtype == OQ_F16 || mask_dtype == OQ_BF16, "oq_attn_decode: mask dtype %d",
+                 mask_dtype);
+    OQ_CHECK_ARG(mask_bstride >= 0 && mask_ld >= 0, "oq_attn_decode: negative mask strides");
+    OQ_CHECK_ARG(oq_aligned16(q) && oq_aligned16(k_cache) && oq_aligned16(v_cache) && oq_aligned16(o) && oq_aligned16(workspace),
+                 "oq_attn_decode: q, o, caches and workspace must be 16-byte aligned");
+    const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
+    OQ_CHECK_ARG(workspace_bytes >= need, "oq_attn_decode: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+    const int ns = dec_splits(bs, nkv, L);
+    const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
+    float* ws = (float*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == OQ_F32) {
+        if (hd == 64) launch_decode_qb<float, 64>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+        else launch_decode_qb<float, 128>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+    } else if (dtype == OQ_BF16) {
+        if (hd == 64) launch_decode_qb<bf16_t, 64>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+        else launch_decode_qb<bf16_t, 128>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+    } else {
+        oq_set_error("oq_attn_decode: dtype %d unsupported", dtype);
+        return OQ_E_UNSUPPORTED;
+    }
+    OQ_CHECK_LAUNCH("oq_attn_decode");
+    return OQ_OK;
+}

@@ -36,12 +36,11 @@ __global__ void rope_kernel(const T* x, T* y, int64_t Tn, int64_t heads, int64_t
         Vec8<float>::load(sn + tt * hd + d0, s1);
         Vec8<float>::load(cs + tt * hd + half + d0, c2);
         Vec8<float>::load(sn + tt * hd + half + d0, s2);
+        if (!inverse) {
+            oq_rope_fwd8(a, b, c1, s1, c2, s2, oa, ob);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (!inverse) {
-                oa[i] = a[i] * c1[i] + (-b[i]) * s1[i];
-                ob[i] = b[i] * c2[i] + a[i] * s2[i];
-            } else {
+            for (int i = 0; i < 8; ++i) {
                 oa[i] = a[i] * c1[i] + b[i] * s2[i];
                 ob[i] = b[i] * c2[i] - a[i] * s1[i];
             }

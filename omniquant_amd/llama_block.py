@@ -18,6 +18,10 @@ from .matmul import QuantMatMul
 from .norm import OmniLlamaRMSNorm
 
 
+#: (theta, head_dim, device) -> full cos / sin tables of the KV-cache path (QuantLlamaAttention._rope_table)
+_ROPE_TABLES = {}
+
+
 def _rope_theta(config):
     rp = getattr(config, "rope_parameters", None)
     if isinstance(rp, dict) and "rope_theta" in rp:
@@ -128,6 +132,23 @@ class QuantLlamaAttention(nn.Module):
         cos, sin = emb.cos().contiguous(), emb.sin().contiguous()
         self._rope_cache = ((T, str(device)), position_ids, None if position_ids is None else position_ids._version, cos, sin)
         return cos, sin
+
+    def _rope_table(self, L, device):
+        """cos / sin [P, hd] f32 over positions 0..P-1, P >= max(L, max_position_embeddings), for the KV-cache path
+        (oq_kv_append gathers rows by position on the device).  The formula of _rope_tables evaluated once per position, so a
+        gathered row equals a freshly computed one bit for bit; shared by the layers of one model (same theta, hd, device)
+        and doubled when a sequence outruns it."""
+        key = (self.rope_theta, self.head_dim, str(device))
+        hit = _ROPE_TABLES.get(key)
+        if hit is not None and hit[0].shape[0] >= L:
+            return hit
+        P = max(int(L), int(self.max_position_embeddings or 0), 2 * hit[0].shape[0] if hit is not None else 0)
+        hd = self.head_dim
+        inv = 1.0 / (self.rope_theta ** (torch.arange(0, hd, 2, dtype=torch.float32, device=device) / hd))
+        fr = torch.outer(torch.arange(P, dtype=torch.float32, device=device), inv)
+        emb = torch.cat((fr, fr), dim=-1)
+        _ROPE_TABLES[key] = (emb.cos().contiguous(), emb.sin().contiguous())
+        return _ROPE_TABLES[key]
 
     def _fused_rope_quant(self, hq):
         """True when q / k / v can take the fused projection -> RoPE -> head-wise quant node: the three head quantisers are
@@ -320,6 +341,8 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
         in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual)."""
         self._packed_check(past_key_value, use_cache, output_attentions)
+        if past_key_value is not None or use_cache:
+            return self._packed_forward_cached(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
         x, back = self._enter(hidden_states)
         a, m = self.self_attn, self.mlp
         bsz, T, _ = x.shape
@@ -335,3 +358,33 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         h = self.post_attention_layernorm(x)
         x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
         return (self._leave(x, back),)
+
+    @torch.no_grad()
+    def _packed_forward_cached(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache):
+        """The packed forward with a KV cache (models/int_llama_layer.py:121-135,177,264-265): q / k rotated at their
+        positions and k / v appended to the cache in one launch, then attention over the whole cache.  Returns (hidden,) plus
+        (present,) -- a PackedKVCache -- when use_cache."""
+        x, back = self._enter(hidden_states)
+        a, m = self.self_attn, self.mlp
+        bsz, T, _ = x.shape
+        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+        cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x)
+        past = cache.length
+        if position_ids is None:
+            pos = torch.arange(past, past + T, dtype=torch.int64, device=x.device)[None]
+        else:
+            pos = position_ids.reshape(-1, position_ids.shape[-1]) if position_ids.dim() == 1 else position_ids
+            if pos.dim() != 2 or pos.shape[1] != T or pos.shape[0] not in (1, bsz):
+                raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
+            pos = pos.to(device=x.device, dtype=torch.int64)
+        cos, sin = a._rope_table(past + T, x.device)
+        h = self.input_layernorm(x)
+        q = a.q_proj(h).view(bsz, T, nh, hd)
+        k = a.k_proj(h).view(bsz, T, nkv, hd)
+        v = a.v_proj(h).view(bsz, T, nkv, hd)
+        attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos)
+        x = a.o_proj(attn.reshape(bsz, T, self.hidden_size), residual=x)
+        h = self.post_attention_layernorm(x)
+        x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
+        out = (self._leave(x, back),)
+        return out + (cache,) if use_cache else out

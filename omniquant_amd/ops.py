@@ -1622,6 +1622,71 @@ class LetVectorsFn(torch.autograd.Function):
         return tuple(pg) + tuple(res[7:]) + (None,) * 8
 
 
+def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None):
+    """Append one step's k / v [bs, Tq, nkv, hd] to rows [past, past + Tq) of the [bs, nkv, cap, hd] caches in ONE launch
+    (csrc/oq_decode.hip), rotating q (into q_out) and k with the cos / sin tables [P, hd] (rows = positions 0..P-1) gathered at
+    `positions` (int64 [1 | bs, Tq]; None = past + t).  cos None: no rotation (OPT).  k_out: optional [bs, Tq, nkv, hd] copy
+    of the rotated k (the prefill's attention reads it)."""
+    bs, Tq, nkv, hd = k.shape
+    if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype:
+        raise C.OQError(f"kv_append: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
+    if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or (k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]) != \
+            (bs, nkv, hd) or k_cache.dtype != k.dtype or v_cache.dtype != k.dtype:
+        raise C.OQError(f"kv_append: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)} {k.dtype}")
+    cap = k_cache.shape[2]
+    if past < 0 or past + Tq > cap:
+        raise C.OQError(f"kv_append: rows [{past}, {past + Tq}) beyond the capacity {cap}")
+    nh = 0
+    if q is not None:
+        nh = q.shape[2]
+        if q.dim() != 4 or tuple(q.shape[:2]) != (bs, Tq) or q.shape[3] != hd or q.dtype != k.dtype:
+            raise C.OQError(f"kv_append: q {tuple(q.shape)} does not fit k {tuple(k.shape)}")
+        q = q.contiguous()
+        q_out = q if q_out is None else q_out
+    P, pbs = 0, 0
+    if cos is not None:
+        if cos.dim() != 2 or cos.shape[1] != hd or tuple(sin.shape) != tuple(cos.shape):
+            raise C.OQError(f"kv_append: cos / sin tables {tuple(cos.shape)} for head_dim {hd}")
+        P = cos.shape[0]
+        if positions is not None:
+            if positions.dim() != 2 or positions.shape[1] != Tq or positions.shape[0] not in (1, bs) or positions.dtype != torch.int64:
+                raise C.OQError(f"kv_append: positions {tuple(positions.shape)} {positions.dtype} (int64 [1 | {bs}, {Tq}])")
+            positions = positions.contiguous()
+            pbs = Tq if positions.shape[0] == bs and bs > 1 else 0
+    k, v = k.contiguous(), v.contiguous()
+    C.call("oq_kv_append", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out), C.ptr(k_cache), C.ptr(v_cache), C.dt(k),
+           bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, C.stream())
+    return q_out
+
+
+def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None):
+    """o [bs, Tq, nh, hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over the first L rows of the [bs, nkv, cap, hd]
+    caches (csrc/oq_decode.hip: split-L streaming, fp32 online softmax, one rounding).  mask: None or additive [bs | 1, 1, Tq, L]
+    in float32 / float16 / bfloat16, read in place on the device (any batch / row stride; a batch of 1 is broadcast)."""
+    bs, Tq, nh, hd = q.shape
+    if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
+            or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+        raise C.OQError(f"decode_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
+    nkv, cap = k_cache.shape[1], k_cache.shape[2]
+    q = q.contiguous()
+    mptr, mdt, mbs, mld = None, 0, 0, 0
+    if mask is not None:
+        if mask.dim() != 4 or mask.shape[1] != 1 or tuple(mask.shape[2:]) != (Tq, L) or mask.shape[0] not in (1, bs):
+            raise C.OQError(f"decode_attention: mask {tuple(mask.shape)} (expected [{bs} | 1, 1, {Tq}, {L}])")
+        if mask.stride(3) != 1:
+            mask = mask.contiguous()
+        mptr, mdt = C.ptr(mask[:1, :1, :1, :1]), C.dt(mask)
+        mbs = mask.stride(0) if mask.shape[0] == bs and bs > 1 else 0
+        mld = mask.stride(2) if Tq > 1 else 0
+    ws_n = C.size_call("oq_attn_decode_workspace", bs, nh, nkv, Tq, int(L), hd)
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
+        workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty_like(q) if out is None else out
+    C.call("oq_attn_decode", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd, cap, int(L),
+           float(scale), mptr, mdt, mbs, mld, C.ptr(workspace), workspace.numel() * workspace.element_size(), C.stream())
+    return o
+
+
 def mask_is_causal(attention_mask):
     """True iff the additive attention mask ([T,T] or [bs,1,T,T]) is exactly the causal one: 0 on/below the diagonal
     and <= -3e4 above it -- finfo(float32).min, or finfo(float16).min = -65504 as transformers builds it for the fp16

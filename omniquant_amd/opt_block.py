@@ -143,11 +143,17 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         a = self.self_attn
         bsz, T, _ = x.shape
         nh, hd = a.num_heads, a.head_dim
+        cached = past_key_value is not None or use_cache
+        # (KV-cache path, models/int_opt_layer.py:110-121,343-344: k / v appended to a PackedKVCache, returned as present)
+        cache = self._kv_cache_in(past_key_value, bsz, T, nh, hd, x) if cached else None
         h = self.self_attn_layer_norm(x) if self.do_layer_norm_before else x
         q = ops.ScaleFn.apply(a.q_proj(h), a.scaling).view(bsz, T, nh, hd)
         k = a.k_proj(h).view(bsz, T, nh, hd)
         v = a.v_proj(h).view(bsz, T, nh, hd)
-        attn = self._packed_attention(q, k, v, attention_mask, 1.0)
+        if cached:
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0)
+        else:
+            attn = self._packed_attention(q, k, v, attention_mask, 1.0)
         x = a.out_proj(attn.reshape(bsz, T, self.embed_dim), residual=x)
         if not self.do_layer_norm_before:
             x = self.self_attn_layer_norm(x)
@@ -155,4 +161,5 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         x = self.fc2(ops.ReluFn.apply(self.fc1(h)), residual=x)
         if not self.do_layer_norm_before:
             x = self.final_layer_norm(x)
-        return (self._leave(x, back),)
+        out = (self._leave(x, back),)
+        return out + (cache,) if use_cache else out

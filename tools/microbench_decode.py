@@ -1,0 +1,211 @@
+"""Microbenchmark of the incremental-decoding kernels (csrc/oq_decode.hip) and of one packed LLaMA-7B decode step.
+
+1. oq_attn_decode (bf16, Tq = 1) at the LLaMA-7B shape (32 / 32 heads of 128) and the LLaMA-2-70B GQA shape (64 / 8), bs 1
+   and 8, L = 512 ... 32768.  Cold caches: each shape rotates through enough distinct K/V caches that one round reads more
+   than the 256 MiB Infinity Cache.  Time per launch from one captured graph of `reps` rounds, replayed under hipEvents.
+   GB/s counts the algorithmic bytes (2 * bs * nkv * L * hd * 2 of K and V; no mask), "frac" is that over the 6.3 TB/s
+   achievable HBM rate (MI355X_MICROARCH.md).  Baseline: what the block would otherwise need -- a [bs, L, nkv, hd] copy of
+   the cache, then AttnScoresFn -> SoftmaxFn -> AttnPVFn (oq_gemm + oq_softmax_fwd; the softmax kernel covers L <= 4096).
+2. One packed LLaMA-7B W4A16g128 block decode step (bs 1, L 2048, bf16): device time per step from a captured graph, the
+   eager host time per forward call, and the HIP launches of the step (C-ABI calls counted on the host).
+   `--step-only --steps N` runs N eager steps and nothing else (for a `rocprofv3 --kernel-trace --stats` run of its own).
+
+usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from omniquant_amd import _capi as C  # noqa: E402
+from omniquant_amd import ops  # noqa: E402
+
+SHAPES = [("7b", 32, 32, 128), ("70b gqa", 64, 8, 128)]
+BS = [1, 8]
+LS = [512, 2048, 8192, 32768]
+COLD_BYTES = 320 << 20           # > 256 MiB Infinity Cache
+HBM_BPS = 6.3e12
+
+
+def timed(fns, reps):
+    """Mean time per launch of `reps` rounds over fns, replayed from one captured graph."""
+    for f in fns:
+        f()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(reps):
+            for f in fns:
+                f()
+    g.replay()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    g.replay()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1000.0 / (reps * len(fns))
+
+
+def kernel_rows(reps, quick, dev):
+    rows = []
+    for name, nh, nkv, hd in SHAPES:
+        for bs in BS:
+            for L in LS:
+                if quick and (bs != 1 or L not in (2048, 8192)):
+                    continue
+                kv_bytes = 2 * bs * nkv * L * hd * 2
+                nsets = max(2, -(-COLD_BYTES // kv_bytes))
+                sets = [(torch.randn(bs, nkv, L, hd, device=dev).bfloat16(), torch.randn(bs, nkv, L, hd, device=dev).bfloat16())
+                        for _ in range(nsets)]
+                q = torch.randn(bs, 1, nh, hd, device=dev).bfloat16()
+                o = torch.empty_like(q)
+                ws_n = C.size_call("oq_attn_decode_workspace", bs, nh, nkv, 1, L, hd)
+                ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+                scale = hd ** -0.5
+                r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, L=L, Tq=1, dtype="bfloat16", cache="cold", sets=nsets)
+
+                def dec(s):
+                    return lambda: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)
+
+                r["decode_us"] = timed([dec(s) for s in sets], reps)
+                r["decode_GBps"] = kv_bytes / r["decode_us"] / 1e3
+                r["decode_frac_hbm"] = r["decode_GBps"] * 1e9 / HBM_BPS
+                if L <= 4096:
+                    def base(s):
+                        def f():
+                            k = s[0].transpose(1, 2).contiguous()          # [bs, L, nkv, hd]: the layout the GEMMs read
+                            v = s[1].transpose(1, 2).contiguous()
+                            p = ops.SoftmaxFn.apply(ops.AttnScoresFn.apply(q, k, False), None, scale, False)
+                            ops.AttnPVFn.apply(p, v, False)
+                        return f
+
+                    with torch.no_grad():
+                        r["baseline_us"] = timed([base(s) for s in sets], reps)
+                    r["speedup"] = r["baseline_us"] / r["decode_us"]
+                rows.append(r)
+                print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+                del sets
+                torch.cuda.empty_cache()
+    return rows
+
+
+def packed_7b_block(dev, L_cap):
+    """A LLaMA-7B block with random W4 g128 AutoGPTQ buffers (the decode step's cost does not depend on their values)."""
+    from omniquant_amd.calibrate import decoder_layer_class, default_args
+    from omniquant_amd.linear import QuantLinear
+    from omniquant_amd.realquant import PackedLinear, _mark_packed
+    from omniquant_amd.synthetic import make_config, make_layer
+    cfg = make_config("llama-7b")
+    args = default_args(wbits=4, abits=16, group_size=128, lwc=True, let=False, epochs=0, nsamples=1, net="llama-7b")
+    blk = decoder_layer_class("llama")(cfg, make_layer(cfg, device=dev, outliers=False), args).to(dev)
+    bits, group = 4, 128
+    for name, m in list(blk.named_modules()):
+        if isinstance(m, QuantLinear):
+            inn, out = m.in_features, m.out_features
+            ng = inn // group
+            p = dict(qweight=torch.randint(-2 ** 31, 2 ** 31 - 1, (inn // 32 * bits, out), dtype=torch.int32, device=dev),
+                     qzeros=torch.randint(-2 ** 31, 2 ** 31 - 1, (ng, out // 32 * bits), dtype=torch.int32, device=dev),
+                     scales=((torch.rand(ng, out, device=dev) + 0.5) * (0.5 / (1 << bits))).half(),
+                     g_idx=torch.arange(inn, dtype=torch.int32, device=dev) // group, bias=None)
+            parent = blk
+            parts = name.split(".")
+            for p_ in parts[:-1]:
+                parent = getattr(parent, p_)
+            setattr(parent, parts[-1], PackedLinear(bits, group, inn, out, p))
+    _mark_packed(blk, 16)
+    blk.compute_dtype = torch.bfloat16
+    return blk, cfg
+
+
+def block_step(dev, reps, steps_only=0):
+    from omniquant_amd.kvcache import PackedKVCache
+    L = 2048
+    blk, cfg = packed_7b_block(dev, L)
+    H, nh = cfg.hidden_size, cfg.num_attention_heads
+    hd = H // nh
+    cache = PackedKVCache(1, nh, hd, torch.bfloat16, dev, capacity=L + max(steps_only, 64) + 8)
+    cache.k.normal_()
+    cache.v.normal_()
+    x = (torch.randn(1, 1, H, device=dev) * 0.5).bfloat16()
+    pos = torch.tensor([[L - 1]], device=dev)
+
+    def step():
+        cache.length = L - 1
+        with torch.no_grad():
+            return blk(x, attention_mask=None, position_ids=pos, past_key_value=cache, use_cache=True)[0]
+
+    step()
+    torch.cuda.synchronize()
+    if steps_only:
+        for _ in range(steps_only):
+            step()
+        torch.cuda.synchronize()
+        return None
+    # launches of one step: every C-ABI call is one or more kernel launches (oq_attn_decode: two)
+    calls = []
+    orig = C.call
+    C.call = lambda name, *a: calls.append(name) or orig(name, *a)
+    try:
+        step()
+    finally:
+        C.call = orig
+    torch.cuda.synchronize()
+    # eager: host time per forward call (enqueue only), and wall time per call with the device drained at the end
+    n = 200
+    t0 = time.perf_counter()
+    for _ in range(n):
+        step()
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    # device time per step from a captured graph of `reps * 10` steps
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(reps * 10):
+            step()
+    g.replay()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    g.replay()
+    b.record()
+    torch.cuda.synchronize()
+    r = dict(what="packed llama-7b W4A16g128 block decode step", bs=1, L=L, dtype="bfloat16",
+             graph_device_us_per_step=a.elapsed_time(b) * 1000.0 / (reps * 10),
+             eager_host_us_per_call=(t1 - t0) * 1e6 / n, eager_wall_us_per_call=(t2 - t0) * 1e6 / n,
+             capi_calls_per_step=len(calls), capi_calls=sorted(set(calls)),
+             hip_launches_per_step=len(calls) + calls.count("oq_attn_decode"))
+    print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--step-only", action="store_true", help="only N eager decode steps of the 7B block (for rocprofv3)")
+    ap.add_argument("--steps", type=int, default=50)
+    a = ap.parse_args()
+    dev = "cuda:0"
+    if not torch.cuda.is_available():
+        raise SystemExit("microbench_decode needs a GPU")
+    C.load()
+    if a.step_only:
+        block_step(dev, a.reps, steps_only=a.steps)
+        return
+    rows = kernel_rows(a.reps, a.quick, dev)
+    rows.append(block_step(dev, a.reps))
+    if a.out:
+        with open(a.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+if __name__ == "__main__":
+    main()
