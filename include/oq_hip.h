@@ -309,6 +309,29 @@ int oq_packed_gemm(const void* x, int x_dtype, int64_t M, int64_t in, int64_t ou
                    const int32_t* qweight, const int32_t* qzeros, const void* scales, const void* bias, const void* addend,
                    void* y, void* stream);
 
+/* ---- W4A4 real-quant inference on the packed 4-bit per-channel AutoGPTQ buffers (csrc/oq_packed_a4.hip).  Value contract,
+ *      output row t, column n:  y[t][n] = s_a[t] s_w[n] sum_k (q_a[t][k] - z_a[t]) (q_w[k][n] - z_w[n]) + bias[n] (+ addend[t][n])
+ *      with the activation codes q_a (int8 0..15, [M, in]), per-row scale s_a, rounded zero-point z_a and code sum Ca
+ *      (ops.IntCodes as the quantiser kernels write them), the weight codes q_w of qweight, z_w = unpacked qzeros + 1 (the
+ *      -1 wrap of a zero of 0 decodes to 16, as dequantize()) and s_w = the fp16 scale.  The integer sum is exact, the fp32
+ *      epilogue is oq_gemm_i8's, so the gemv and the codes + oq_gemm_i8 route give the same bits for the same row.
+ *   oq_packed_gemv_a4: 1 <= M <= 16; y / addend f32 or bf16; bias fp16 [out] or NULL.  in, out multiples of 32, in <= 65536,
+ *      per-channel (one qzeros / scales row).  Workspace: oq_packed_gemv_a4_workspace() bytes (int32 split partials).
+ *   oq_packed_codes:   qweight -> codes int8 [out, in] (k-contiguous) and w_scale / w_zp / w_csum f32 [out]: the B operand
+ *      of oq_gemm_i8 (b_bits 4).  Integer atomics (global) accumulate w_csum: exact, order-free.
+ *   oq_quant_codes:    per-token asymmetric quantiser (quantize/quantizer.py:84-147) of x [rows, cols] (f32 / bf16, cols a
+ *      multiple of 8) with integer codes: y (optional, y_dtype) = the fake-quant values, scale / zp / csum [rows], codes int8
+ *      [rows, cols]; csum is NaN for a row whose scale is 0 / NaN.  nbits 2..7. ------------------------------------------- */
+int64_t oq_packed_gemv_a4_workspace(int64_t M, int64_t in, int64_t out);
+int oq_packed_gemv_a4(const void* codes, const float* a_scale, const float* a_zp, const float* a_csum, int64_t M, int64_t in,
+                      int64_t out, const int32_t* qweight, const int32_t* qzeros, const void* scales, const void* bias,
+                      const void* addend, int addend_dtype, void* y, int y_dtype, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int oq_packed_codes(const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t in, int64_t out, void* codes,
+                    float* w_scale, float* w_zp, float* w_csum, void* stream);
+int oq_quant_codes(const void* x, int dtype, int64_t rows, int64_t cols, int nbits, void* y, int y_dtype, float* scale, float* zp,
+                   void* codes, float* csum, void* stream);
+
 /* ---- incremental decoding of the packed blocks (models/int_llama_layer.py:121-135,143-163,177 and
  *      models/int_opt_layer.py:110-121: rotary embedding at position_ids, torch.cat with past_key_value, attention of the new
  *      queries against the whole cache).  The cache is [bs, nkv, cap, hd] (rows [0, L) valid), dtype OQ_BF16 or OQ_F32.
@@ -327,6 +350,15 @@ int oq_packed_gemm(const void* x, int x_dtype, int64_t M, int64_t in, int64_t ou
 int oq_kv_append(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache, int dtype,
                  int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past, const float* cos, const float* sin,
                  int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream);
+/*   oq_kv_append_quant: oq_kv_append for W4A4 blocks.  q / k / v in in_dtype (f32, or the output dtype); the same rotation
+ *      (q and k, from the fp32 values), then the per-(token, head) asymmetric nbits quantiser over hd (quantize/quantizer.py:
+ *      122-147) of the fp32 result: q -> q_out, k -> cache rows [past, past+Tq) and k_out, v (not rotated) -> cache rows and
+ *      v_out, all in dtype (f32 / bf16).  The caches may be NULL (then k_out and v_out are required); k_out / v_out may be
+ *      NULL.  hd 64 or 128. */
+int oq_kv_append_quant(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                       void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                       int64_t past, const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                       int nbits, void* stream);
 int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd);
 int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
                    int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,

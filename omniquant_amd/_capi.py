@@ -69,6 +69,11 @@ SIGNATURES = {
     "oq_packed_dequant": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i32, _vp],
     "oq_packed_gemv": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "oq_packed_gemm": [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "oq_packed_gemv_a4": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp],
+    "oq_packed_codes": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "oq_quant_codes": [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "oq_kv_append_quant": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _vp,
+                           _i64, _vp, _i64, _i32, _vp],
     "oq_kv_append": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i64, _vp, _i64,
                      _vp],
     "oq_attn_decode": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _i32, _i64, _i64, _vp, _i64,
@@ -113,6 +118,7 @@ SIZE_FUNCS = {"oq_fakequant_bwd_workspace": [_i64, _i64], "oq_norm_bwd_workspace
               "oq_colsum_workspace": [_i64, _i64], "oq_gemm_workspace": [_i64, _i64, _i64, _i32, _i64, _i32], "oq_rope_quant_supported": [_i32, _i32],
               "oq_norm_quant_supported": [_i32, _i64], "oq_norm_quant_bwd_workspace": [_i64, _i64],
               "oq_fakequant_codes_supported": [_i64, _i64, _i32, _i32], "oq_packed_gemv_workspace": [_i64, _i64, _i64, _i32],
+              "oq_packed_gemv_a4_workspace": [_i64, _i64, _i64],
               "oq_attn_decode_workspace": [_i64, _i32, _i32, _i64, _i64, _i32]}
 
 _lib = None

@@ -54,17 +54,19 @@ class QuantBlockMixin:
     # weight-only inference path on the PackedLinear kernels (no fake quant, no autograd, no graph capture).
     def _packed_check(self, past_key_value=None, use_cache=False, output_attentions=False):
         from ._capi import OQError
-        bits = self.__dict__["_oq_packed"]["act_bits"]
-        if bits < 16:
+        mark = self.__dict__["_oq_packed"]
+        bits = mark["act_bits"]
+        if bits < 16 and not mark.get("act_quant"):
             raise OQError(f"packed block with {bits}-bit activation quantisers: real quantisation is weight-only (AutoGPTQ's "
                           "QuantLinear has no activation quantiser); evaluate W*A<16 models with the fake-quant block instead")
         if output_attentions:
             raise NotImplementedError("the packed inference path does not return attention weights")
 
     # ---- incremental decoding (past_key_value / use_cache) on the packed path ----------------------------------------------
-    def _kv_cache_in(self, past_key_value, bsz, Tq, nkv, hd, x):
+    def _kv_cache_in(self, past_key_value, bsz, Tq, nkv, hd, x, head_bits=None):
         """The PackedKVCache this forward appends to: a new one (prefill), the caller's (appended in place) or a copy of a
-        reference-layout (k, v) tuple converted to the compute dtype (the caller's tensors are left alone)."""
+        reference-layout (k, v) tuple converted to the compute dtype (the caller's tensors are left alone).  head_bits (W4A4
+        blocks, whose cache holds head-quantised k / v): the tuple's raw rows are quantised once, on import."""
         from ._capi import OQError
         from .kvcache import PackedKVCache
         if hd not in (64, 128):
@@ -80,7 +82,7 @@ class QuantBlockMixin:
             k = past_key_value[0]
             if not torch.is_tensor(k) or k.dim() != 4 or (k.shape[0], k.shape[1], k.shape[3]) != (bsz, nkv, hd):
                 raise OQError(f"past_key_value {tuple(getattr(k, 'shape', ()))}: expected [{bsz}, {nkv}, T, {hd}]")
-            return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq)
+            return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq, head_bits=head_bits)
         raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
 
     def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None):

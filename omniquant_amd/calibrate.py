@@ -46,7 +46,7 @@ def default_args(**kw):
     """Hyper-parameters with the reference's defaults (main.py:193-229)."""
     a = SimpleNamespace(wbits=4, abits=4, group_size=None, alpha=0.5, let_lr=5e-3, lwc_lr=1e-2, wd=0.0, epochs=10,
                         let=False, lwc=False, aug_loss=False, symmetric=False, nsamples=128, batch_size=1,
-                        deactive_amp=False, resume=None, real_quant=False, output_dir=None, net="llama-7b")
+                        deactive_amp=False, resume=None, real_quant=False, real_quant_act=False, output_dir=None, net="llama-7b")
     for k, v in kw.items():
         setattr(a, k, v)
     return quant_params_from_args(a)
@@ -321,7 +321,8 @@ def calibrate_layers(layers, config, args, inps, attention_mask, position_ids=No
                 torch.save(omni_parameters, os.path.join(args.output_dir, "omni_parameters.pth"))
         if getattr(args, "real_quant", False):
             from .realquant import pack_block
-            pack_block(qlayer, args.wbits)         # quantize/omniquant.py:255-278
+            # quantize/omniquant.py:255-278; real_quant_act: the W4A4 integer path (realquant.check_act_quant_eligible)
+            pack_block(qlayer, args.wbits, act_quant=bool(getattr(args, "real_quant_act", False)))
         qlayers.append(qlayer if keep_on_device else qlayer.to("cpu"))
     return qlayers, omni_parameters, all_losses, (quant_inps, fp_inps)
 

@@ -215,5 +215,17 @@ __device__ __forceinline__ void oq_rope_fwd8(const float (&a)[8], const float (&
     }
 }
 
+// fp32 epilogue of the integer-exact linears (oq_gemm_i8, oq_packed_gemv_a4): acc = the exact integer sum of stored
+// a-codes x stored w-codes, za / zw the rounded zero-points minus the stored-code offsets, ca / cw the stored code sums,
+//     sum = acc - za * cw - zw * (ca - K * za),   y = s_a * s_w * sum + bias
+// ONE expression for every kernel (the library builds with -ffp-contract=off): a row's result does not depend on which
+// kernel served it, nor on M.
+__device__ __forceinline__ float oq_i8_a2(float ca, float K, float za) { return ca - K * za; }
+__device__ __forceinline__ float oq_i8_epilogue(float acc, float za, float a2, float sa, float zw, float cw, float sw, float bias) {
+    float inner = fmaf(-za, cw, acc);
+    inner = fmaf(-zw, a2, inner);
+    return fmaf(sa * sw, inner, bias);
+}
+
 static inline int oq_dtype_size(int dt) { return dt == OQ_F32 ? 4 : 2; }
 static inline bool oq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -10,6 +10,7 @@
 // (max, sum, accumulator) partials to a workspace that a second launch combines in split order.  No atomics: for one
 // problem the bits do not change from launch to launch, nor with the cache capacity.
 #include "oq_common.h"
+#include "oq_quant_dev.h"
 
 namespace {
 
@@ -65,6 +66,98 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const T* q, const T* k, 
         }
         Vec8<T>::store(dst + d0, a);
         Vec8<T>::store(dst + half + d0, c);
+        if (dst2) {
+            Vec8<T>::store(dst2 + d0, a);
+            Vec8<T>::store(dst2 + half + d0, c);
+        }
+    }
+}
+
+// ---- KV append with the head quantisers (W4A4 packed blocks): the rotation of kv_append_kernel from the fp32 inputs, then
+//      the per-(token, head) asymmetric quantiser over hd (quantize/quantizer.py:122-147, oq_quant_dev.h arithmetic) on the
+//      fp32 result.  The hd / 16 work items of one (token, head) are consecutive lanes of one wave, so min / max reduce with
+//      DPP inside that lane group.  Cache pointers may be NULL (no-cache forward: q_out / k_out / v_out only). ---------------
+template <typename TIN, typename T>
+__global__ void __launch_bounds__(256) kv_append_quant_kernel(const TIN* q, const TIN* k, const TIN* v, T* q_out, T* k_out, T* v_out,
+                                                              T* kc, T* vc, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                                              int64_t cap, int64_t past, const float* cs, const float* sn, int64_t P,
+                                                              const int64_t* pos, int64_t pos_bs, int nbits, float inv_q) {
+    const int half = hd / 2, hv = hd / 16;
+    const int nslot = nh + 2 * nkv;
+    const int64_t n = bs * Tq * nslot * hv;
+    const float Q = (float)((1 << nbits) - 1);
+    for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) {
+        const int d0 = (int)(it % hv) * 8;
+        int64_t r = it / hv;
+        const int slot = (int)(r % nslot);
+        r /= nslot;
+        const int64_t t = r % Tq, b = r / Tq;
+        const TIN* src;
+        T* dst;
+        T* dst2;
+        bool rot = cs != nullptr;
+        if (slot < nh) {
+            src = q + ((b * Tq + t) * nh + slot) * hd;
+            dst = q_out + ((b * Tq + t) * nh + slot) * hd;
+            dst2 = nullptr;
+        } else if (slot < nh + nkv) {
+            const int h = slot - nh;
+            src = k + ((b * Tq + t) * nkv + h) * hd;
+            dst = kc ? kc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst2 = k_out ? k_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
+        } else {
+            const int h = slot - nh - nkv;
+            src = v + ((b * Tq + t) * nkv + h) * hd;
+            dst = vc ? vc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst2 = v_out ? v_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
+            rot = false;
+        }
+        float a[8], c[8];
+        Vec8<TIN>::load(src + d0, a);
+        Vec8<TIN>::load(src + half + d0, c);
+        if (rot) {
+            int64_t p = pos ? pos[b * pos_bs + t] : past + t;
+            p = p < 0 ? 0 : (p >= P ? P - 1 : p);
+            float c1[8], s1[8], c2[8], s2[8], oa[8], ob[8];
+            Vec8<float>::load(cs + p * hd + d0, c1);
+            Vec8<float>::load(sn + p * hd + d0, s1);
+            Vec8<float>::load(cs + p * hd + half + d0, c2);
+            Vec8<float>::load(sn + p * hd + half + d0, s2);
+            oq_rope_fwd8(a, c, c1, s1, c2, s2, oa, ob);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { a[i] = oa[i]; c[i] = ob[i]; }
+        }
+        float hi = -INFINITY, lo = INFINITY, bad = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            hi = fmaxf(hi, fmaxf(a[i], c[i]));
+            lo = fminf(lo, fminf(a[i], c[i]));
+            if (a[i] != a[i] || c[i] != c[i]) bad = 1.f;
+        }
+        hi = wave_max(hi, hv);
+        lo = wave_min(lo, hv);
+        bad = wave_max(bad, hv);
+        if (bad != 0.f) { hi = NAN; lo = NAN; }
+        float inv_s = 0.f;
+        const QP qp = make_qp(hi, lo, false, 0.f, 0.f, nbits, 0, inv_q, &inv_s);
+        const bool regular = qp.s != 0.f && fabsf(qp.s) <= 3.4028234663852886e38f && bad == 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            float& x = i < 8 ? a[i] : c[i - 8];
+            if (regular) {
+                float tq;
+                const float rq = rne_div(x, qp.s, inv_s, &tq);
+                x = (__builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q) - qp.z) * qp.s;
+            } else {
+                float u = rne_ste(x / qp.s) + qp.z;
+                u = (u != u) ? u : fminf(fmaxf(u, 0.f), Q);
+                x = (u - qp.z) * qp.s;
+            }
+        }
+        if (dst) {
+            Vec8<T>::store(dst + d0, a);
+            Vec8<T>::store(dst + half + d0, c);
+        }
         if (dst2) {
             Vec8<T>::store(dst2 + d0, a);
             Vec8<T>::store(dst2 + half + d0, c);
@@ -354,5 +447,46 @@ extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_
         return OQ_E_UNSUPPORTED;
     }
     OQ_CHECK_LAUNCH("oq_attn_decode");
+    return OQ_OK;
+}
+
+extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                                  void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                  int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                                  int64_t pos_bstride, int nbits, void* stream) {
+    OQ_CHECK_ARG(k && v, "oq_kv_append_quant: null k / v");
+    OQ_CHECK_ARG(!q || q_out, "oq_kv_append_quant: q without q_out");
+    OQ_CHECK_ARG(!k_cache == !v_cache, "oq_kv_append_quant: the k and v caches go together");
+    OQ_CHECK_ARG(k_cache || (k_out && v_out), "oq_kv_append_quant: no destination for k / v (caches or k_out / v_out)");
+    OQ_CHECK_ARG(bs > 0 && Tq > 0 && nkv > 0 && nh >= 0 && (q || nh == 0), "oq_kv_append_quant: bad shape");
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_kv_append_quant: head_dim %d (64 or 128)", hd);
+    OQ_CHECK_ARG(nbits >= 2 && nbits <= 8, "oq_kv_append_quant: %d-bit head quantiser (2..8)", nbits);
+    OQ_CHECK_ARG(!k_cache || (past >= 0 && past + Tq <= cap), "oq_kv_append_quant: rows [%lld, %lld) exceed the capacity %lld",
+                 (long long)past, (long long)(past + Tq), (long long)cap);
+    OQ_CHECK_ARG(!cos == !sin, "oq_kv_append_quant: cos and sin go together");
+    OQ_CHECK_ARG(!cos || (P > 0 && oq_aligned16(cos) && oq_aligned16(sin)), "oq_kv_append_quant: cos/sin tables must be 16-byte aligned, P > 0");
+    OQ_CHECK_ARG(pos_bstride >= 0, "oq_kv_append_quant: pos_bstride");
+    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "oq_kv_append_quant: dtype %d (f32 or bf16)", dtype);
+    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "oq_kv_append_quant: input dtype %d (f32 or the output dtype)", in_dtype);
+    const void* ptrs[] = {q, k, v, q_out, k_out, v_out, k_cache, v_cache};
+    for (const void* p : ptrs) OQ_CHECK_ARG(!p || oq_aligned16(p), "oq_kv_append_quant: tensors must be 16-byte aligned");
+    const int64_t n = bs * Tq * (nh + 2 * nkv) * (hd / 16);
+    const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
+    const float inv_q = 1.0f / (float)((1 << nbits) - 1);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == OQ_F32) {
+        hipLaunchKernelGGL((kv_append_quant_kernel<float, float>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k,
+                           (const float*)v, (float*)q_out, (float*)k_out, (float*)v_out, (float*)k_cache, (float*)v_cache, bs, Tq, nh,
+                           nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
+    } else if (in_dtype == OQ_F32) {
+        hipLaunchKernelGGL((kv_append_quant_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k,
+                           (const float*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, (bf16_t*)k_cache, (bf16_t*)v_cache, bs,
+                           Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
+    } else {
+        hipLaunchKernelGGL((kv_append_quant_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
+                           (const bf16_t*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, (bf16_t*)k_cache, (bf16_t*)v_cache,
+                           bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
+    }
+    OQ_CHECK_LAUNCH("oq_kv_append_quant");
     return OQ_OK;
 }

@@ -10,7 +10,7 @@
 // operand bytes per MAC) into int32 accumulators -- exact -- and the epilogue applies, in fp32,
 //     sum = acc - za'[t] * Cw[n] - zw'[n] * (Ca[t] - K * za'[t])      za' = z_a - off_a, zw' = z_w - off_w,
 //                                                                      Ca[t] = sum_k stored a-codes, Cw[n] likewise
-// then the two scales, bias and the residual.  (The bf16 form rounds (q - z) * s of BOTH operands to 8 bits of mantissa first,
+// then the two scales, bias and the residual (oq_i8_epilogue, oq_common.h: the one expression oq_packed_gemv_a4 shares).  (The bf16 form rounds (q - z) * s of BOTH operands to 8 bits of mantissa first,
 // which is what flips ~3 % of the next 4-bit rounding decisions downstream -- DESIGN.md section 4.)
 //
 // Structure = gemm_bf16_p3_kernel of oq_gemm.hip with both operands k-contiguous: 256x128 output tile, K-tile of 128 BYTES per
@@ -233,14 +233,12 @@ __global__ void __launch_bounds__(512) gemm_i8_p3_kernel(GemmI8P p) {
         if (m >= p.M || !ncol) continue;
         const float s_a = p.sa[m];
         const float z_a = p.za[m] - p.off_a;
-        const float a2 = p.ca[m] - Kf * z_a;
+        const float a2 = oq_i8_a2(p.ca[m], Kf, z_a);
         float v[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const float ai = (float)(r < 4 ? lo[r] : hi[r - 4]);
-            float inner = fmaf(-z_a, cw[r], ai);
-            inner = fmaf(-zw[r], a2, inner);
-            v[r] = fmaf(s_a * sw[r], inner, bv[r]);
+            v[r] = oq_i8_epilogue(ai, z_a, a2, s_a, zw[r], cw[r], sw[r], bv[r]);
         }
         TOUT* dst = C + m * p.ldc + n;
         if (p.addend) {
@@ -266,10 +264,8 @@ __global__ void __launch_bounds__(256) gemm_i8_ref_kernel(GemmI8P p) {
     int acc = 0;
     for (int64_t k = 0; k < p.K; ++k) acc += (int)ar[k] * (int)br[k];
     const float z_a = p.za[m] - p.off_a, z_w = p.zw[n] - p.off_w;
-    const float a2 = p.ca[m] - (float)p.K * z_a;
-    float inner = fmaf(-z_a, p.cw[n], (float)acc);
-    inner = fmaf(-z_w, a2, inner);
-    float v = fmaf(p.sa[m] * p.sw[n], inner, p.bias ? p.bias[n] : 0.f);
+    const float a2 = oq_i8_a2(p.ca[m], (float)p.K, z_a);
+    float v = oq_i8_epilogue((float)acc, z_a, a2, p.sa[m], z_w, p.cw[n], p.sw[n], p.bias ? p.bias[n] : 0.f);
     TOUT* C = reinterpret_cast<TOUT*>(p.c);
     if (p.addend)
         v += p.add_f32 ? reinterpret_cast<const float*>(p.addend)[m * p.ldc + n]

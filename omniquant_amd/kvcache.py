@@ -73,9 +73,10 @@ class PackedKVCache:
                 f"capacity={self.capacity})")
 
     @classmethod
-    def from_tuple(cls, kv, dtype=None, capacity=None):
+    def from_tuple(cls, kv, dtype=None, capacity=None, head_bits=None):
         """A cache holding copies of the reference-layout (k, v), each [bs, nkv, T, hd] (any float dtype, converted once);
-        the tensors passed in are never modified."""
+        the tensors passed in are never modified.  head_bits (W4A4 blocks): the rows are quantised per (token, head) over hd on
+        that grid as they are imported (ops.kv_append_quant without rotation), which is what the block's own appends store."""
         if len(kv) != 2:
             raise OQError(f"past_key_value: expected (k, v), got {len(kv)} tensors")
         k, v = kv
@@ -85,7 +86,12 @@ class PackedKVCache:
             raise OQError("past_key_value: GPU tensors expected (no CPU fallback)")
         bs, nkv, T, hd = k.shape
         c = cls(bs, nkv, hd, dtype or k.dtype, k.device, max(int(capacity or 0), T))
-        if T:
+        if T and head_bits is not None:
+            from . import ops
+            src = c.dtype if k.dtype == c.dtype else torch.float32
+            kt, vt = (t.transpose(1, 2).to(src).contiguous() for t in (k, v))         # [bs, T, nkv, hd], fresh copies
+            ops.kv_append_quant(kt, vt, head_bits, c.dtype, k_cache=c.k, v_cache=c.v, past=0)
+        elif T:
             c.k[:, :, :T].copy_(k)
             c.v[:, :, :T].copy_(v)
         c.length = T

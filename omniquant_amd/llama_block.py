@@ -341,6 +341,8 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
         in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual)."""
         self._packed_check(past_key_value, use_cache, output_attentions)
+        if self.__dict__["_oq_packed"].get("act_quant"):
+            return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
         if past_key_value is not None or use_cache:
             return self._packed_forward_cached(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
         x, back = self._enter(hidden_states)
@@ -387,4 +389,93 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         h = self.post_attention_layernorm(x)
         x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
         out = (self._leave(x, back),)
+        return out + (cache,) if use_cache else out
+
+    # ---- W4A4 packed inference (realquant.pack_block(..., act_quant=True)) ---------------------------------------------------
+    def _norm_codes(self, norm, x2):
+        """IntCodes of the 4-bit per-token quantiser applied to norm(x2): the fused norm -> quantiser kernel where it covers the
+        row (512 .. 8192 columns), else the norm in the compute dtype, then the quantiser (as the fake-quant block does)."""
+        from .norm import _f32_cached
+        w, b = _f32_cached(norm, "weight"), _f32_cached(norm, "bias")
+        if ops.norm_quant_supported(x2, 4):
+            stash = {"want_int": True}
+            ops.NormQuantFn.apply(x2, w, b, norm.variance_epsilon, False, 4, stash)
+            return stash["int"]
+        return ops.act_codes(norm(x2), 4)
+
+    @torch.no_grad()
+    def _packed_forward_a4(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache):
+        """W4A4 real-quant inference: norm -> 4-bit per-token codes (one set for q, k, v) -> integer q / k / v linears (fp32
+        outputs: nothing is rounded to 16 bits in front of the head quantisers) -> RoPE + head quantisers (+ KV-cache append)
+        in one launch -> attention on the quantised q / k / v -> codes -> integer o_proj (+ residual in its epilogue) -> norm
+        -> codes -> integer gate / up -> silu * up -> codes -> integer down_proj (+ residual).  With a cache, the cache holds
+        the head-quantised k / v (models/int_llama_layer.py:132-142 quantises the cached rows at every step; per-token
+        quantisation depends on the row alone, so quantising once at append gives the same values).  The no-cache forward
+        and a prefill with use_cache run the same launches: bit-identical outputs.
+        The residual stream (the input, the o_proj output + residual, the block output before its one rounding to the input's
+        dtype) stays float32 in the bf16 mode too: both norms feed a 4-bit rounding decision."""
+        from ._capi import OQError
+        x, _ = self._enter(hidden_states)
+        a, m = self.self_attn, self.mlp
+        bsz, T, H = x.shape
+        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+        if hd not in (64, 128):
+            raise OQError(f"the W4A4 packed path covers head_dim 64 and 128 (oq_kv_append_quant), not {hd}")
+        cd = x.dtype
+        x2 = ops.cast(hidden_states, torch.float32).reshape(bsz * T, H)      # (exact widening of the caller's values)
+        hint = self._norm_codes(self.input_layernorm, x2)
+        f32 = torch.float32
+        q = a.q_proj.forward_codes(hint, out_dtype=f32).view(bsz, T, nh, hd)
+        k = a.k_proj.forward_codes(hint, out_dtype=f32).view(bsz, T, nkv, hd)
+        v = a.v_proj.forward_codes(hint, out_dtype=f32).view(bsz, T, nkv, hd)
+        scale = 1.0 / math.sqrt(hd)
+        qr = torch.empty((bsz, T, nh, hd), dtype=cd, device=x.device)
+        cache = None
+        if past_key_value is not None or use_cache:
+            cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x, head_bits=4)
+            past = cache.length
+            L = past + T
+            if position_ids is None:
+                pos = torch.arange(past, L, dtype=torch.int64, device=x.device)[None]
+            else:
+                pos = position_ids.reshape(-1, position_ids.shape[-1]) if position_ids.dim() == 1 else position_ids
+                if pos.dim() != 2 or pos.shape[1] != T or pos.shape[0] not in (1, bsz):
+                    raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
+                pos = pos.to(device=x.device, dtype=torch.int64)
+            if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[0] not in (1, bsz)
+                                               or tuple(attention_mask.shape[1:]) != (1, T, L)):
+                raise ValueError(f"Attention mask should be of size {(bsz, 1, T, L)}, but is {attention_mask.size()}")
+            cos, sin = a._rope_table(L, x.device)
+            cache.reserve(T)
+            kr = vr = None
+            if past == 0:
+                kr, vr = torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device), torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device)
+            ops.kv_append_quant(k, v, 4, cd, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos,
+                                sin=sin, positions=pos)
+            cache.length = L
+            if past == 0:
+                mask = attention_mask
+                if mask is not None and mask.shape[0] != bsz:
+                    mask = mask.expand(bsz, 1, T, L)
+                attn = self._packed_attention(qr, kr, vr, mask, scale)
+            else:
+                attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
+        else:
+            cos, sin = a._rope_tables(position_ids, T, x.device)
+            kr, vr = torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device), torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device)
+            ops.kv_append_quant(k, v, 4, cd, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin)
+            attn = self._packed_attention(qr, kr, vr, attention_mask, scale)
+        x2 = a.o_proj.forward_codes(ops.act_codes(attn.reshape(bsz * T, H), 4), residual=x2, out_dtype=torch.float32)
+        hint = self._norm_codes(self.post_attention_layernorm, x2)
+        pre = ops.int_pre_dtype(cd, "mlp")
+        gate = m.gate_proj.forward_codes(hint, out_dtype=pre)
+        up = m.up_proj.forward_codes(hint, out_dtype=pre)
+        if ops.silu_mul_quant_supported(gate, 4):
+            stash = {"want_int": True}
+            ops.SiluMulQuantFn.apply(gate, up, 4, stash)
+            dint = stash["int"]
+        else:
+            dint = ops.act_codes(ops.SiluMulFn.apply(gate, up), 4)
+        x2 = m.down_proj.forward_codes(dint, residual=x2, out_dtype=torch.float32)
+        out = (ops.cast(x2.view(bsz, T, H), hidden_states.dtype),)
         return out + (cache,) if use_cache else out

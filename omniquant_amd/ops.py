@@ -1659,6 +1659,68 @@ def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=
     return q_out
 
 
+def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, q=None, q_out=None, k_out=None, v_out=None,
+                    cos=None, sin=None, positions=None):
+    """kv_append for the W4A4 packed blocks (csrc/oq_decode.hip, oq_kv_append_quant): q / k / v [bs, Tq, heads, hd] in float32
+    or out_dtype are rotated (q, k; cos None: no rotation) exactly as kv_append rotates them, from fp32, then quantised per
+    (token, head) over hd on the nbits asymmetric grid; the fake-quant values go, in out_dtype, to q_out, to cache rows
+    [past, past + Tq) and to k_out / v_out.  The caches may be None (the no-cache forward: k_out and v_out then)."""
+    bs, Tq, nkv, hd = k.shape
+    if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
+        raise C.OQError(f"kv_append_quant: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
+    cap = 0
+    if k_cache is not None:
+        if v_cache is None or k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or \
+                (k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]) != (bs, nkv, hd) or k_cache.dtype != out_dtype \
+                or v_cache.dtype != out_dtype:
+            raise C.OQError(f"kv_append_quant: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)}")
+        cap = k_cache.shape[2]
+        if past < 0 or past + Tq > cap:
+            raise C.OQError(f"kv_append_quant: rows [{past}, {past + Tq}) beyond the capacity {cap}")
+    for t, shp in ((k_out, k.shape), (v_out, k.shape)):
+        if t is not None and (tuple(t.shape) != tuple(shp) or t.dtype != out_dtype or not t.is_contiguous()):
+            raise C.OQError("kv_append_quant: k_out / v_out must be contiguous tensors of k's shape in the output dtype")
+    nh = 0
+    if q is not None:
+        nh = q.shape[2]
+        if q.dim() != 4 or tuple(q.shape[:2]) != (bs, Tq) or q.shape[3] != hd or q.dtype != k.dtype:
+            raise C.OQError(f"kv_append_quant: q {tuple(q.shape)} does not fit k {tuple(k.shape)}")
+        if q_out is None or tuple(q_out.shape) != tuple(q.shape) or q_out.dtype != out_dtype:
+            raise C.OQError("kv_append_quant: q_out must be a tensor of q's shape in the output dtype")
+        q = q.contiguous()
+    P, pbs = 0, 0
+    if cos is not None:
+        if cos.dim() != 2 or cos.shape[1] != hd or tuple(sin.shape) != tuple(cos.shape):
+            raise C.OQError(f"kv_append_quant: cos / sin tables {tuple(cos.shape)} for head_dim {hd}")
+        P = cos.shape[0]
+        if positions is not None:
+            if positions.dim() != 2 or positions.shape[1] != Tq or positions.shape[0] not in (1, bs) or positions.dtype != torch.int64:
+                raise C.OQError(f"kv_append_quant: positions {tuple(positions.shape)} {positions.dtype} (int64 [1 | {bs}, {Tq}])")
+            positions = positions.contiguous()
+            pbs = Tq if positions.shape[0] == bs and bs > 1 else 0
+    k, v = k.contiguous(), v.contiguous()
+    C.call("oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache),
+           C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs,
+           int(nbits), C.stream())
+    return q_out
+
+
+def act_codes(x2, nbits, out=None):
+    """Per-token asymmetric quantiser (quantize/quantizer.py:84-147) of the rows of x2 [rows, cols] (float32 / bfloat16) ->
+    IntCodes (csrc/oq_packed_a4.hip, oq_quant_codes: the arithmetic of every quantiser kernel).  out: optional destination of
+    the fake-quant values (float32 / bfloat16 [rows, cols])."""
+    if x2.dim() != 2 or x2.dtype not in (torch.float32, torch.bfloat16):
+        raise C.OQError(f"act_codes: rows of float32 / bfloat16 expected, got {tuple(x2.shape)} {x2.dtype}")
+    rows, cols = x2.shape
+    x2 = x2.contiguous()
+    codes = torch.empty((rows, cols), dtype=torch.int8, device=x2.device)
+    vec = torch.empty((3, rows), dtype=torch.float32, device=x2.device)
+    if rows:
+        C.call("oq_quant_codes", C.ptr(x2), C.dt(x2), rows, cols, int(nbits), C.ptr(out), C.dt(out) if out is not None else 0,
+               C.fptr(vec[0]), C.fptr(vec[1]), C.ptr(codes), C.fptr(vec[2]), C.stream())
+    return IntCodes(codes, vec[0], vec[1], vec[2], int(nbits))
+
+
 def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None):
     """o [bs, Tq, nh, hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over the first L rows of the [bs, nkv, cap, hd]
     caches (csrc/oq_decode.hip: split-L streaming, fp32 online softmax, one rounding).  mask: None or additive [bs | 1, 1, Tq, L]
