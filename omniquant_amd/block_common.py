@@ -85,10 +85,22 @@ class QuantBlockMixin:
             return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq, head_bits=head_bits)
         raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
 
-    def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None):
+    @staticmethod
+    def _positions(position_ids, past, bsz, T, device):
+        """position_ids (None: past .. past + T - 1; [T]; [1 | bs, T]) as the int64 [1 | bs, T] tensor the append gathers at."""
+        if position_ids is None:
+            return torch.arange(past, past + T, dtype=torch.int64, device=device)[None]
+        pos = position_ids.reshape(-1, position_ids.shape[-1]) if position_ids.dim() == 1 else position_ids
+        if pos.dim() != 2 or pos.shape[1] != T or pos.shape[0] not in (1, bsz):
+            raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
+        return pos.to(device=device, dtype=torch.int64)
+
+    def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None, head_bits=None):
         """Attention of this step's q [bs, Tq, nh, hd] over the cache plus this step's k / v, which are appended to it (rotated
         by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
-        (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation."""
+        (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation.
+        head_bits (W4A4 blocks): q / k / v (float32 or the cache's dtype) also pass the per-(token, head) quantiser of that
+        width in the append's launch, so the cache holds, and the attention reads, the quantised values in the cache's dtype."""
         from . import ops
         bsz, Tq = q.shape[0], q.shape[1]
         past = cache.length
@@ -98,16 +110,23 @@ class QuantBlockMixin:
             raise ValueError(f"Attention mask should be of size {(bsz, 1, Tq, L)}, but is {attention_mask.size()}")
         cache.reserve(Tq)
         rot = cos is not None
-        qr = torch.empty_like(q) if rot else q
-        kr = torch.empty_like(k) if (rot and past == 0) else None
-        ops.kv_append(k, v, cache.k, cache.v, past, q=q if rot else None, q_out=qr if rot else None, k_out=kr, cos=cos, sin=sin,
-                      positions=positions)
+        # copies of this step's rows for the prefill's attention, of every tensor the append changes
+        if head_bits is None:
+            qr = torch.empty_like(q) if rot else q
+            kr, vr = torch.empty_like(k) if (rot and past == 0) else None, None
+            ops.kv_append(k, v, cache.k, cache.v, past, q=q if rot else None, q_out=qr if rot else None, k_out=kr, cos=cos, sin=sin,
+                          positions=positions)
+        else:
+            qr = torch.empty(q.shape, dtype=cache.dtype, device=q.device)
+            kr, vr = (torch.empty(k.shape, dtype=cache.dtype, device=q.device) for _ in range(2)) if past == 0 else (None, None)
+            ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr, k_out=kr,
+                                v_out=vr, cos=cos, sin=sin, positions=positions)
         cache.length = L
         if past == 0:
             mask = attention_mask
             if mask is not None and mask.shape[0] != bsz:
                 mask = mask.expand(bsz, 1, Tq, L)
-            return self._packed_attention(qr, kr if rot else k, v, mask, scale)
+            return self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
         return ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
 
     @staticmethod

@@ -1,5 +1,6 @@
 // Incremental-decoding kernels of the packed (real-quant) blocks on gfx950: the KV-cache append with RoPE at arbitrary
-// positions, and attention of 1..Tq query rows against the cached K/V.
+// positions (one kernel template; its QUANT instantiations add the W4A4 head quantisers and serve oq_kv_append_quant), and
+// attention of 1..Tq query rows against the cached K/V.
 // Reference lines: models/int_llama_layer.py:121-135,177 (rotary embedding gathered at position_ids, torch.cat with
 // past_key_value, present_key_value) and :143-163 (scores, mask, softmax, PV); models/int_opt_layer.py:110-121,151-170.
 //
@@ -15,77 +16,37 @@
 namespace {
 
 // ---- KV append: q [bs,Tq,nh,hd], k / v [bs,Tq,nkv,hd] -> rotated q (q_out), rotated k (cache rows past.., and k_out),
-//      plain v (cache).  One work item = 8 elements of a head's first half and the 8 partners of its second half. -------------
-template <typename T>
-__global__ void __launch_bounds__(256) kv_append_kernel(const T* q, const T* k, const T* v, T* q_out, T* k_out, T* kc, T* vc,
-                                                        int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
-                                                        int64_t past, const float* cs, const float* sn, int64_t P,
-                                                        const int64_t* pos, int64_t pos_bs) {
-    const int half = hd / 2, hv = hd / 16;
-    const int nslot = nh + 2 * nkv;
-    const int64_t n = bs * Tq * nslot * hv;
-    for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) {
-        const int d0 = (int)(it % hv) * 8;
-        int64_t r = it / hv;
-        const int slot = (int)(r % nslot);
-        r /= nslot;
-        const int64_t t = r % Tq, b = r / Tq;
-        const T* src;
-        T* dst;
-        T* dst2 = nullptr;
-        bool rot = cs != nullptr;
-        if (slot < nh) {
-            src = q + ((b * Tq + t) * nh + slot) * hd;
-            dst = q_out + ((b * Tq + t) * nh + slot) * hd;
-        } else if (slot < nh + nkv) {
-            const int h = slot - nh;
-            src = k + ((b * Tq + t) * nkv + h) * hd;
-            dst = kc + ((b * nkv + h) * cap + past + t) * hd;
-            if (k_out) dst2 = k_out + ((b * Tq + t) * nkv + h) * hd;
-        } else {
-            const int h = slot - nh - nkv;
-            src = v + ((b * Tq + t) * nkv + h) * hd;
-            dst = vc + ((b * nkv + h) * cap + past + t) * hd;
-            rot = false;
-        }
-        float a[8], c[8];
-        Vec8<T>::load(src + d0, a);
-        Vec8<T>::load(src + half + d0, c);
-        if (rot) {
-            // positions outside [0, P) are clamped to the table, never read out of bounds (the host sizes P >= past + Tq)
-            int64_t p = pos ? pos[b * pos_bs + t] : past + t;
-            p = p < 0 ? 0 : (p >= P ? P - 1 : p);
-            float c1[8], s1[8], c2[8], s2[8], oa[8], ob[8];
-            Vec8<float>::load(cs + p * hd + d0, c1);
-            Vec8<float>::load(sn + p * hd + d0, s1);
-            Vec8<float>::load(cs + p * hd + half + d0, c2);
-            Vec8<float>::load(sn + p * hd + half + d0, s2);
-            oq_rope_fwd8(a, c, c1, s1, c2, s2, oa, ob);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { a[i] = oa[i]; c[i] = ob[i]; }
-        }
-        Vec8<T>::store(dst + d0, a);
-        Vec8<T>::store(dst + half + d0, c);
-        if (dst2) {
-            Vec8<T>::store(dst2 + d0, a);
-            Vec8<T>::store(dst2 + half + d0, c);
-        }
-    }
-}
+//      plain v (cache, and v_out).  One work item = 8 elements of a head's first half and the 8 partners of its second half.
+//      QUANT (W4A4 packed blocks): the rotation runs on the fp32 inputs, then the per-(token, head) asymmetric quantiser over
+//      hd (quantize/quantizer.py:122-147, oq_quant_dev.h arithmetic) on the fp32 result.  The hd / 16 work items of one
+//      (token, head) are consecutive lanes of one wave, so min / max reduce with DPP inside that lane group.  The plain
+//      append is the TIN == T, QUANT = false instantiation: it carries none of the quantiser.  Cache pointers may be NULL
+//      (no-cache forward: q_out / k_out / v_out only); so may k_out / v_out. ------------------------------------------------
+struct AppendP {
+    const void *q, *k, *v;
+    void *q_out, *k_out, *v_out, *kc, *vc;
+    int64_t bs, Tq;
+    int nh, nkv, hd;
+    int64_t cap, past;
+    const float *cs, *sn;
+    int64_t P;
+    const int64_t* pos;
+    int64_t pos_bs;
+    int nbits;
+    float inv_q;
+};
 
-// ---- KV append with the head quantisers (W4A4 packed blocks): the rotation of kv_append_kernel from the fp32 inputs, then
-//      the per-(token, head) asymmetric quantiser over hd (quantize/quantizer.py:122-147, oq_quant_dev.h arithmetic) on the
-//      fp32 result.  The hd / 16 work items of one (token, head) are consecutive lanes of one wave, so min / max reduce with
-//      DPP inside that lane group.  Cache pointers may be NULL (no-cache forward: q_out / k_out / v_out only). ---------------
-template <typename TIN, typename T>
-__global__ void __launch_bounds__(256) kv_append_quant_kernel(const TIN* q, const TIN* k, const TIN* v, T* q_out, T* k_out, T* v_out,
-                                                              T* kc, T* vc, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
-                                                              int64_t cap, int64_t past, const float* cs, const float* sn, int64_t P,
-                                                              const int64_t* pos, int64_t pos_bs, int nbits, float inv_q) {
+template <typename TIN, typename T, bool QUANT>
+__global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
+    const int hd = p.hd, nh = p.nh, nkv = p.nkv;
+    const int64_t Tq = p.Tq, cap = p.cap, past = p.past;
+    const TIN* q = (const TIN*)p.q;
+    const TIN* k = (const TIN*)p.k;
+    const TIN* v = (const TIN*)p.v;
+    T *q_out = (T*)p.q_out, *k_out = (T*)p.k_out, *v_out = (T*)p.v_out, *kc = (T*)p.kc, *vc = (T*)p.vc;
     const int half = hd / 2, hv = hd / 16;
     const int nslot = nh + 2 * nkv;
-    const int64_t n = bs * Tq * nslot * hv;
-    const float Q = (float)((1 << nbits) - 1);
+    const int64_t n = p.bs * Tq * nslot * hv;
     for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) {
         const int d0 = (int)(it % hv) * 8;
         int64_t r = it / hv;
@@ -95,7 +56,7 @@ __global__ void __launch_bounds__(256) kv_append_quant_kernel(const TIN* q, cons
         const TIN* src;
         T* dst;
         T* dst2;
-        bool rot = cs != nullptr;
+        bool rot = p.cs != nullptr;
         if (slot < nh) {
             src = q + ((b * Tq + t) * nh + slot) * hd;
             dst = q_out + ((b * Tq + t) * nh + slot) * hd;
@@ -116,42 +77,46 @@ __global__ void __launch_bounds__(256) kv_append_quant_kernel(const TIN* q, cons
         Vec8<TIN>::load(src + d0, a);
         Vec8<TIN>::load(src + half + d0, c);
         if (rot) {
-            int64_t p = pos ? pos[b * pos_bs + t] : past + t;
-            p = p < 0 ? 0 : (p >= P ? P - 1 : p);
+            // positions outside [0, P) are clamped to the table, never read out of bounds (the host sizes P >= past + Tq)
+            int64_t ps = p.pos ? p.pos[b * p.pos_bs + t] : past + t;
+            ps = ps < 0 ? 0 : (ps >= p.P ? p.P - 1 : ps);
             float c1[8], s1[8], c2[8], s2[8], oa[8], ob[8];
-            Vec8<float>::load(cs + p * hd + d0, c1);
-            Vec8<float>::load(sn + p * hd + d0, s1);
-            Vec8<float>::load(cs + p * hd + half + d0, c2);
-            Vec8<float>::load(sn + p * hd + half + d0, s2);
+            Vec8<float>::load(p.cs + ps * hd + d0, c1);
+            Vec8<float>::load(p.sn + ps * hd + d0, s1);
+            Vec8<float>::load(p.cs + ps * hd + half + d0, c2);
+            Vec8<float>::load(p.sn + ps * hd + half + d0, s2);
             oq_rope_fwd8(a, c, c1, s1, c2, s2, oa, ob);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { a[i] = oa[i]; c[i] = ob[i]; }
         }
-        float hi = -INFINITY, lo = INFINITY, bad = 0.f;
+        if constexpr (QUANT) {
+            const float Q = (float)((1 << p.nbits) - 1);
+            float hi = -INFINITY, lo = INFINITY, bad = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            hi = fmaxf(hi, fmaxf(a[i], c[i]));
-            lo = fminf(lo, fminf(a[i], c[i]));
-            if (a[i] != a[i] || c[i] != c[i]) bad = 1.f;
-        }
-        hi = wave_max(hi, hv);
-        lo = wave_min(lo, hv);
-        bad = wave_max(bad, hv);
-        if (bad != 0.f) { hi = NAN; lo = NAN; }
-        float inv_s = 0.f;
-        const QP qp = make_qp(hi, lo, false, 0.f, 0.f, nbits, 0, inv_q, &inv_s);
-        const bool regular = qp.s != 0.f && fabsf(qp.s) <= 3.4028234663852886e38f && bad == 0.f;
+            for (int i = 0; i < 8; ++i) {
+                hi = fmaxf(hi, fmaxf(a[i], c[i]));
+                lo = fminf(lo, fminf(a[i], c[i]));
+                if (a[i] != a[i] || c[i] != c[i]) bad = 1.f;
+            }
+            hi = wave_max(hi, hv);
+            lo = wave_min(lo, hv);
+            bad = wave_max(bad, hv);
+            if (bad != 0.f) { hi = NAN; lo = NAN; }
+            float inv_s = 0.f;
+            const QP qp = make_qp(hi, lo, false, 0.f, 0.f, p.nbits, 0, p.inv_q, &inv_s);
+            const bool regular = qp.s != 0.f && fabsf(qp.s) <= 3.4028234663852886e38f && bad == 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            float& x = i < 8 ? a[i] : c[i - 8];
-            if (regular) {
-                float tq;
-                const float rq = rne_div(x, qp.s, inv_s, &tq);
-                x = (__builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q) - qp.z) * qp.s;
-            } else {
-                float u = rne_ste(x / qp.s) + qp.z;
-                u = (u != u) ? u : fminf(fmaxf(u, 0.f), Q);
-                x = (u - qp.z) * qp.s;
+            for (int i = 0; i < 16; ++i) {
+                float& x = i < 8 ? a[i] : c[i - 8];
+                if (regular) {
+                    float tq;
+                    const float rq = rne_div(x, qp.s, inv_s, &tq);
+                    x = (__builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q) - qp.z) * qp.s;
+                } else {
+                    float u = rne_ste(x / qp.s) + qp.z;
+                    u = (u != u) ? u : fminf(fmaxf(u, 0.f), Q);
+                    x = (u - qp.z) * qp.s;
+                }
             }
         }
         if (dst) {
@@ -163,6 +128,41 @@ __global__ void __launch_bounds__(256) kv_append_quant_kernel(const TIN* q, cons
             Vec8<T>::store(dst2 + half + d0, c);
         }
     }
+}
+
+template <typename TIN, typename T, bool QUANT>
+void launch_append(const AppendP& p, hipStream_t st) {
+    const int64_t n = p.bs * p.Tq * (p.nh + 2 * p.nkv) * (p.hd / 16);
+    const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
+    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT>), dim3(grid), dim3(256), 0, st, p);
+}
+
+// The checks, the grid and the dtype dispatch both ABI entry points share (fn: the entry point's name for the messages).
+// The caller has checked what is its own: which pointers it requires, head_dim, nbits and the dtype pairs it admits.
+template <bool QUANT>
+int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* stream) {
+    OQ_CHECK_ARG(!p.q || p.q_out, "%s: q without q_out", fn);
+    OQ_CHECK_ARG(p.bs > 0 && p.Tq > 0 && p.nkv > 0 && p.nh >= 0 && (p.q || p.nh == 0), "%s: bad shape", fn);
+    OQ_CHECK_ARG(!p.kc || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
+                 (long long)p.past, (long long)(p.past + p.Tq), (long long)p.cap);
+    OQ_CHECK_ARG(!p.cs == !p.sn, "%s: cos and sin go together", fn);
+    OQ_CHECK_ARG(!p.cs || (p.P > 0 && oq_aligned16(p.cs) && oq_aligned16(p.sn)), "%s: cos/sin tables must be 16-byte aligned, P > 0", fn);
+    OQ_CHECK_ARG(p.pos_bs >= 0, "%s: pos_bstride", fn);
+    const void* ptrs[] = {p.q, p.k, p.v, p.q_out, p.k_out, p.v_out, p.kc, p.vc};
+    for (const void* ptr : ptrs) OQ_CHECK_ARG(!ptr || oq_aligned16(ptr), "%s: tensors must be 16-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == OQ_F32 && in_dtype == OQ_F32) {
+        launch_append<float, float, QUANT>(p, st);
+    } else if (dtype == OQ_BF16 && in_dtype == OQ_BF16) {
+        launch_append<bf16_t, bf16_t, QUANT>(p, st);
+    } else if constexpr (QUANT) {
+        launch_append<float, bf16_t, true>(p, st);       // f32 -> bf16: the only other pair the quantising entry admits
+    } else {
+        oq_set_error("%s: dtype %d unsupported", fn, dtype);
+        return OQ_E_UNSUPPORTED;
+    }
+    OQ_CHECK_LAUNCH(fn);
+    return OQ_OK;
 }
 
 // ---- decode attention ----------------------------------------------------------------------------------------------------
@@ -382,33 +382,9 @@ extern "C" int oq_kv_append(const void* q, const void* k, const void* v, void* q
                             const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                             void* stream) {
     OQ_CHECK_ARG(k && v && k_cache && v_cache, "oq_kv_append: null pointer");
-    OQ_CHECK_ARG(!q || q_out, "oq_kv_append: q without q_out");
-    OQ_CHECK_ARG(bs > 0 && Tq > 0 && nkv > 0 && nh >= 0 && (q || nh == 0), "oq_kv_append: bad shape");
     OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "oq_kv_append: head_dim %d must be a multiple of 16", hd);
-    OQ_CHECK_ARG(past >= 0 && past + Tq <= cap, "oq_kv_append: rows [%lld, %lld) exceed the capacity %lld", (long long)past,
-                 (long long)(past + Tq), (long long)cap);
-    OQ_CHECK_ARG(!cos == !sin, "oq_kv_append: cos and sin go together");
-    OQ_CHECK_ARG(!cos || (P > 0 && oq_aligned16(cos) && oq_aligned16(sin)), "oq_kv_append: cos/sin tables must be 16-byte aligned, P > 0");
-    OQ_CHECK_ARG(pos_bstride >= 0, "oq_kv_append: pos_bstride");
-    const void* ptrs[] = {q, k, v, q_out, k_out, k_cache, v_cache};
-    for (const void* p : ptrs) OQ_CHECK_ARG(!p || oq_aligned16(p), "oq_kv_append: tensors must be 16-byte aligned");
-    const int64_t n = bs * Tq * (nh + 2 * nkv) * (hd / 16);
-    const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == OQ_F32) {
-        hipLaunchKernelGGL((kv_append_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v,
-                           (float*)q_out, (float*)k_out, (float*)k_cache, (float*)v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin,
-                           P, pos, pos_bstride);
-    } else if (dtype == OQ_BF16) {
-        hipLaunchKernelGGL((kv_append_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
-                           (const bf16_t*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)k_cache, (bf16_t*)v_cache, bs, Tq, nh, nkv, hd,
-                           cap, past, cos, sin, P, pos, pos_bstride);
-    } else {
-        oq_set_error("oq_kv_append: dtype %d unsupported", dtype);
-        return OQ_E_UNSUPPORTED;
-    }
-    OQ_CHECK_LAUNCH("oq_kv_append");
-    return OQ_OK;
+    const AppendP p{q, k, v, q_out, k_out, nullptr, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, 0, 0.f};
+    return kv_append<false>("oq_kv_append", p, dtype, dtype, stream);
 }
 
 extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd) {
@@ -455,38 +431,14 @@ extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, i
                                   int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P, const int64_t* pos,
                                   int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(k && v, "oq_kv_append_quant: null k / v");
-    OQ_CHECK_ARG(!q || q_out, "oq_kv_append_quant: q without q_out");
     OQ_CHECK_ARG(!k_cache == !v_cache, "oq_kv_append_quant: the k and v caches go together");
     OQ_CHECK_ARG(k_cache || (k_out && v_out), "oq_kv_append_quant: no destination for k / v (caches or k_out / v_out)");
-    OQ_CHECK_ARG(bs > 0 && Tq > 0 && nkv > 0 && nh >= 0 && (q || nh == 0), "oq_kv_append_quant: bad shape");
+    // (the DPP reduction over the hd / 16 lanes of a head needs a power-of-two lane group inside one row of 16)
     OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_kv_append_quant: head_dim %d (64 or 128)", hd);
     OQ_CHECK_ARG(nbits >= 2 && nbits <= 8, "oq_kv_append_quant: %d-bit head quantiser (2..8)", nbits);
-    OQ_CHECK_ARG(!k_cache || (past >= 0 && past + Tq <= cap), "oq_kv_append_quant: rows [%lld, %lld) exceed the capacity %lld",
-                 (long long)past, (long long)(past + Tq), (long long)cap);
-    OQ_CHECK_ARG(!cos == !sin, "oq_kv_append_quant: cos and sin go together");
-    OQ_CHECK_ARG(!cos || (P > 0 && oq_aligned16(cos) && oq_aligned16(sin)), "oq_kv_append_quant: cos/sin tables must be 16-byte aligned, P > 0");
-    OQ_CHECK_ARG(pos_bstride >= 0, "oq_kv_append_quant: pos_bstride");
     OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "oq_kv_append_quant: dtype %d (f32 or bf16)", dtype);
     OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "oq_kv_append_quant: input dtype %d (f32 or the output dtype)", in_dtype);
-    const void* ptrs[] = {q, k, v, q_out, k_out, v_out, k_cache, v_cache};
-    for (const void* p : ptrs) OQ_CHECK_ARG(!p || oq_aligned16(p), "oq_kv_append_quant: tensors must be 16-byte aligned");
-    const int64_t n = bs * Tq * (nh + 2 * nkv) * (hd / 16);
-    const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-    const float inv_q = 1.0f / (float)((1 << nbits) - 1);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == OQ_F32) {
-        hipLaunchKernelGGL((kv_append_quant_kernel<float, float>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k,
-                           (const float*)v, (float*)q_out, (float*)k_out, (float*)v_out, (float*)k_cache, (float*)v_cache, bs, Tq, nh,
-                           nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
-    } else if (in_dtype == OQ_F32) {
-        hipLaunchKernelGGL((kv_append_quant_kernel<float, bf16_t>), dim3(grid), dim3(256), 0, st, (const float*)q, (const float*)k,
-                           (const float*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, (bf16_t*)k_cache, (bf16_t*)v_cache, bs,
-                           Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
-    } else {
-        hipLaunchKernelGGL((kv_append_quant_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k,
-                           (const bf16_t*)v, (bf16_t*)q_out, (bf16_t*)k_out, (bf16_t*)v_out, (bf16_t*)k_cache, (bf16_t*)v_cache,
-                           bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, nbits, inv_q);
-    }
-    OQ_CHECK_LAUNCH("oq_kv_append_quant");
-    return OQ_OK;
+    const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
+                    nbits, 1.0f / (float)((1 << nbits) - 1)};
+    return kv_append<true>("oq_kv_append_quant", p, in_dtype, dtype, stream);
 }

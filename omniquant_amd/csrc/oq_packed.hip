@@ -23,7 +23,10 @@
 //                      registers and written to LDS as MFMA fragments; v_mfma_f32_16x16x32_f16 (fp16 x, exact fp16 weight)
 //                      or _bf16 (bf16 x, bf16-rounded weight).  Double-buffered LDS, next tile's loads in flight under the
 //                      MFMAs, one barrier per K-step.  fp32 epilogue: + bias + addend, one rounding to x's dtype.
+// The qzeros field decode, the layout checks, the GEMV split plan and the M -> MM dispatch are oq_packed_dev.h's, shared
+// with oq_packed_a4.hip.
 #include "oq_common.h"
+#include "oq_packed_dev.h"
 
 namespace {
 
@@ -38,16 +41,6 @@ __device__ __forceinline__ int code_at(const uint32_t (&w)[BITS], int j) {
     uint32_t v = w[wi] >> off;
     if (off + BITS > 32) v |= w[wi + 1] << (32 - off);
     return (int)(v & ((1u << BITS) - 1u));
-}
-
-// stored zero code of output column n in one qzeros row (out/32*bits words); the caller adds 1
-__device__ __forceinline__ int zero_at(const uint32_t* row, int64_t n, int bits) {
-    const int64_t bp = n * bits;
-    const int64_t wi = bp >> 5;
-    const int off = (int)(bp & 31);
-    uint32_t v = row[wi] >> off;
-    if (off + bits > 32) v |= row[wi + 1] << (32 - off);
-    return (int)(v & ((1u << bits) - 1u));
 }
 
 // the contract value (fp16, returned widened to f32 exactly); BF: rounded once more to bf16
@@ -89,9 +82,8 @@ __global__ void __launch_bounds__(256) packed_dequant_kernel(const uint32_t* qw,
 // ---------------------------------------------------------------------------------------------------------------------
 // GEMV (M <= 16)
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int GV_COLS = 256;         // output columns per block: 64 lanes x 4
+constexpr int GV_COLS = PK_COLS;     // output columns per block: 64 lanes x 4
 constexpr int GV_KMAX = 512;         // input channels per block (x slice in LDS as f32: 16 rows x 512 x 4 B = 32 KiB)
-constexpr int GV_TARGET_BLOCKS = 512;
 
 struct GemvP {
     const void* x;
@@ -105,18 +97,6 @@ struct GemvP {
     int64_t M, K, N, group;
     int kb_per, splits;
 };
-
-// splits of the contraction (a function of the shape only: the result does not depend on the device)
-int gemv_splits(int64_t K, int64_t N, int* kb_per) {
-    const int64_t KB = K / 32, tiles = (N + GV_COLS - 1) / GV_COLS;
-    int64_t s = (GV_TARGET_BLOCKS + tiles - 1) / tiles;
-    const int64_t smin = (KB + GV_KMAX / 32 - 1) / (GV_KMAX / 32);
-    if (s < smin) s = smin;
-    if (s > KB) s = KB;
-    const int64_t per = (KB + s - 1) / s;
-    *kb_per = (int)per;
-    return (int)((KB + per - 1) / per);
-}
 
 template <typename TX>
 __device__ __forceinline__ void store_out(const GemvP& p, int64_t m, int64_t n, float v) {
@@ -390,17 +370,6 @@ __global__ void __launch_bounds__(256, 2) packed_gemm_kernel(PGemmP p) {
     }
 }
 
-int check_layout(const char* fn, const void* qweight, const void* qzeros, const void* scales, int64_t in, int64_t out,
-                 int64_t group, int bits) {
-    OQ_CHECK_ARG(qweight && qzeros && scales, "%s: null pointer", fn);
-    OQ_CHECK_ARG(bits == 2 || bits == 3 || bits == 4 || bits == 8, "%s: bits %d (2, 3, 4 or 8)", fn, bits);
-    OQ_CHECK_ARG(in > 0 && out > 0 && in % 32 == 0 && out % 32 == 0, "%s: in=%lld out=%lld (multiples of 32)", fn,
-                 (long long)in, (long long)out);
-    OQ_CHECK_ARG(group > 0 && in % group == 0 && (group == in || group % 32 == 0),
-                 "%s: group=%lld (in, or a divisor of in=%lld that is a multiple of 32)", fn, (long long)group, (long long)in);
-    return OQ_OK;
-}
-
 #define OQ_BITS_SWITCH(bits, ...)                              \
     switch (bits) {                                            \
         case 2: { constexpr int B_ = 2; __VA_ARGS__; } break;  \
@@ -410,15 +379,9 @@ int check_layout(const char* fn, const void* qweight, const void* qzeros, const 
     }
 
 template <int BITS, typename TX>
-void launch_gemv(const GemvP& p, int mm, hipStream_t st) {
+void launch_gemv(const GemvP& p, hipStream_t st) {
     const dim3 grid((unsigned)((p.N + GV_COLS - 1) / GV_COLS), (unsigned)p.splits);
-    switch (mm) {
-        case 1: hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, 1>), grid, dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, 2>), grid, dim3(256), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, 4>), grid, dim3(256), 0, st, p); break;
-        case 8: hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, 8>), grid, dim3(256), 0, st, p); break;
-        default: hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, 16>), grid, dim3(256), 0, st, p); break;
-    }
+    OQ_MM_SWITCH(p.M, hipLaunchKernelGGL((packed_gemv_kernel<BITS, TX, MM_>), grid, dim3(256), 0, st, p))
     if (p.splits > 1)
         hipLaunchKernelGGL((packed_gemv_reduce_kernel<TX>), dim3((unsigned)((p.M * p.N + 255) / 256)), dim3(256), 0, st, p);
 }
@@ -451,7 +414,7 @@ extern "C" int64_t oq_packed_gemv_workspace(int64_t M, int64_t in, int64_t out, 
     (void)bits;
     if (M <= 0 || in <= 0 || out <= 0 || in % 32 != 0) return 0;
     int per;
-    const int s = gemv_splits(in, out, &per);
+    const int s = packed_splits(in, out, GV_KMAX / 32, &per);
     return s > 1 ? (int64_t)s * M * out * 4 : 0;
 }
 
@@ -466,16 +429,15 @@ extern "C" int oq_packed_gemv(const void* x, int x_dtype, int64_t M, int64_t in,
                  "oq_packed_gemv: x / qweight must be 16-byte and scales 8-byte aligned");
     GemvP p{x, (const uint32_t*)qweight, (const uint32_t*)qzeros, scales, bias, addend, y, (float*)workspace, M, in, out, group,
             0, 0};
-    p.splits = gemv_splits(in, out, &p.kb_per);
+    p.splits = packed_splits(in, out, GV_KMAX / 32, &p.kb_per);
     const int64_t need = p.splits > 1 ? (int64_t)p.splits * M * out * 4 : 0;
     OQ_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr),
                  "oq_packed_gemv: workspace of %lld bytes needed (oq_packed_gemv_workspace), %lld given", (long long)need,
                  (long long)workspace_bytes);
-    const int mm = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
     hipStream_t st = (hipStream_t)stream;
     OQ_BITS_SWITCH(bits, {
-        if (x_dtype == OQ_F16) launch_gemv<B_, f16_t>(p, mm, st);
-        else launch_gemv<B_, bf16_t>(p, mm, st);
+        if (x_dtype == OQ_F16) launch_gemv<B_, f16_t>(p, st);
+        else launch_gemv<B_, bf16_t>(p, st);
     })
     OQ_CHECK_LAUNCH("oq_packed_gemv");
     return OQ_OK;

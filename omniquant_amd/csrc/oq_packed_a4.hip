@@ -23,13 +23,12 @@
 //                      and Cw [out], a complete ops.IntCodes of the weight; the caller then runs oq_gemm_i8.
 //   oq_quant_codes     the per-token quantiser with integer codes for rows the fused quantiser kernels do not take (they
 //                      need 512+ columns): one wave per row, the same oq_quant_dev.h arithmetic.
+// zero4_at, the layout checks, the GEMV split plan and the M -> MM dispatch are oq_packed_dev.h's, shared with oq_packed.hip.
 #include "oq_common.h"
+#include "oq_packed_dev.h"
 #include "oq_quant_dev.h"
 
 namespace {
-
-// stored zero code of output column n in one qzeros row (4-bit, out/8 words); the caller adds 1
-__device__ __forceinline__ int zero4_at(const uint32_t* row, int64_t n) { return (int)((row[n >> 3] >> ((n & 7) * 4)) & 15u); }
 
 // 8 int8 codes (0..15) -> one nibble word, nibble j = byte j
 __device__ __forceinline__ uint32_t pack_nibbles(uint32_t lo, uint32_t hi) {
@@ -58,9 +57,9 @@ __device__ __forceinline__ uint32_t dot8(uint32_t a, uint32_t b, uint32_t c) { r
 // ---------------------------------------------------------------------------------------------------------------------
 // GEMV (1 <= M <= 16)
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int A4_COLS = 256;              // output columns per workgroup: 64 lanes x 4
+constexpr int A4_COLS = PK_COLS;          // output columns per workgroup: 64 lanes x 4
 constexpr int A4_WMAX = 256;              // packed activation words per row and workgroup (a K slice of 2048 channels)
-constexpr int A4_TARGET_BLOCKS = 512;
+constexpr int A4_KBMAX = A4_WMAX / 4;     // the same in 32-channel blocks of 4 words: packed_splits' unit
 
 struct A4P {
     const int8_t* codes;
@@ -75,19 +74,6 @@ struct A4P {
     int64_t M, K, N;
     int w_per, splits, add_f32, y_f32;
 };
-
-// splits of the contraction: a function of the shape only (never of the device), multiples of 4 words
-int a4_splits(int64_t K, int64_t N, int* w_per) {
-    const int64_t KW = K / 8, tiles = (N + A4_COLS - 1) / A4_COLS;
-    int64_t s = (A4_TARGET_BLOCKS + tiles - 1) / tiles;
-    const int64_t smin = (KW + A4_WMAX - 1) / A4_WMAX;
-    if (s < smin) s = smin;
-    if (s > KW / 4) s = KW / 4;
-    int64_t per = (KW + s - 1) / s;
-    per = (per + 3) / 4 * 4;
-    *w_per = (int)per;
-    return (int)((KW + per - 1) / per);
-}
 
 __device__ __forceinline__ void a4_store(const A4P& p, int64_t m, int64_t n, uint32_t acc, uint32_t cw) {
     const float s_a = p.sa[m], z_a = p.za[m];
@@ -326,14 +312,13 @@ __global__ void __launch_bounds__(256) quant_codes_kernel(const TIN* x, int64_t 
 extern "C" int64_t oq_packed_gemv_a4_workspace(int64_t M, int64_t in, int64_t out) {
     if (M <= 0 || in <= 0 || out <= 0 || in % 32 != 0) return 0;
     int per;
-    const int s = a4_splits(in, out, &per);
+    const int s = packed_splits(in, out, A4_KBMAX, &per);
     return s > 1 ? (int64_t)s * (M + 1) * out * 4 : 0;
 }
 
+// the 4-bit per-channel layout (check_layout) plus what the integer kernels need
 static int check_a4(const char* fn, const int32_t* qweight, const int32_t* qzeros, const void* scales, int64_t in, int64_t out) {
-    OQ_CHECK_ARG(qweight && qzeros && scales, "%s: null weight buffer", fn);
-    OQ_CHECK_ARG(in > 0 && out > 0 && in % 32 == 0 && out % 32 == 0, "%s: in=%lld out=%lld (multiples of 32)", fn, (long long)in,
-                 (long long)out);
+    if (int rc = check_layout(fn, qweight, qzeros, scales, in, out, in, 4)) return rc;
     OQ_CHECK_ARG(in <= (1ll << 16), "%s: in=%lld too long for the integer accumulation", fn, (long long)in);
     OQ_CHECK_ARG(oq_aligned16(qweight), "%s: qweight must be 16-byte aligned", fn);
     return OQ_OK;
@@ -354,18 +339,15 @@ extern "C" int oq_packed_gemv_a4(const void* codes, const float* a_scale, const 
     p.qw = (const uint32_t*)qweight; p.qz = (const uint32_t*)qzeros; p.scales = (const f16_t*)scales; p.bias = (const f16_t*)bias;
     p.addend = addend; p.add_f32 = addend_dtype == OQ_F32; p.y = y; p.y_f32 = y_dtype == OQ_F32;
     p.ws = (int32_t*)workspace; p.M = M; p.K = in; p.N = out;
-    p.splits = a4_splits(in, out, &p.w_per);
+    p.splits = packed_splits(in, out, A4_KBMAX, &p.w_per);
+    p.w_per *= 4;                             // whole blocks: a multiple of 4 words, as the kernel's 16-B activation reads need
     const int64_t need = p.splits > 1 ? (int64_t)p.splits * (M + 1) * out * 4 : 0;
     OQ_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr),
                  "oq_packed_gemv_a4: workspace of %lld bytes needed (oq_packed_gemv_a4_workspace), %lld given", (long long)need,
                  (long long)workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((out + A4_COLS - 1) / A4_COLS), (unsigned)p.splits);
-    if (M <= 1) hipLaunchKernelGGL((packed_gemv_a4_kernel<1>), grid, dim3(256), 0, st, p);
-    else if (M <= 2) hipLaunchKernelGGL((packed_gemv_a4_kernel<2>), grid, dim3(256), 0, st, p);
-    else if (M <= 4) hipLaunchKernelGGL((packed_gemv_a4_kernel<4>), grid, dim3(256), 0, st, p);
-    else if (M <= 8) hipLaunchKernelGGL((packed_gemv_a4_kernel<8>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((packed_gemv_a4_kernel<16>), grid, dim3(256), 0, st, p);
+    OQ_MM_SWITCH(M, hipLaunchKernelGGL((packed_gemv_a4_kernel<MM_>), grid, dim3(256), 0, st, p))
     if (p.splits > 1)
         hipLaunchKernelGGL(packed_gemv_a4_reduce_kernel, dim3((unsigned)((M * out + 255) / 256)), dim3(256), 0, st, p);
     OQ_CHECK_LAUNCH("oq_packed_gemv_a4");

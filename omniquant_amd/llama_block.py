@@ -339,52 +339,31 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
     @torch.no_grad()
     def _packed_forward(self, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache):
         """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
-        in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual)."""
+        in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual).  With a KV cache (past_key_value or use_cache;
+        models/int_llama_layer.py:121-135,177,264-265) q / k are rotated at their positions and k / v appended to the cache in one
+        launch, then attention runs over the whole cache.  Returns (hidden,) plus (present,) -- a PackedKVCache -- when use_cache."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if self.__dict__["_oq_packed"].get("act_quant"):
             return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
+        x, back = self._enter(hidden_states)
+        a, m = self.self_attn, self.mlp
+        bsz, T, _ = x.shape
+        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+        cache = None
         if past_key_value is not None or use_cache:
-            return self._packed_forward_cached(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
-        x, back = self._enter(hidden_states)
-        a, m = self.self_attn, self.mlp
-        bsz, T, _ = x.shape
-        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+            cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x)
+            pos = self._positions(position_ids, cache.length, bsz, T, x.device)
+            cos, sin = a._rope_table(cache.length + T, x.device)
         h = self.input_layernorm(x)
         q = a.q_proj(h).view(bsz, T, nh, hd)
         k = a.k_proj(h).view(bsz, T, nkv, hd)
         v = a.v_proj(h).view(bsz, T, nkv, hd)
-        cos, sin = a._rope_tables(position_ids, T, x.device)
-        q, k = ops.RopeFn.apply(q, cos, sin), ops.RopeFn.apply(k, cos, sin)
-        attn = self._packed_attention(q, k, v, attention_mask, 1.0 / math.sqrt(hd))
-        x = a.o_proj(attn.reshape(bsz, T, self.hidden_size), residual=x)
-        h = self.post_attention_layernorm(x)
-        x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
-        return (self._leave(x, back),)
-
-    @torch.no_grad()
-    def _packed_forward_cached(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache):
-        """The packed forward with a KV cache (models/int_llama_layer.py:121-135,177,264-265): q / k rotated at their
-        positions and k / v appended to the cache in one launch, then attention over the whole cache.  Returns (hidden,) plus
-        (present,) -- a PackedKVCache -- when use_cache."""
-        x, back = self._enter(hidden_states)
-        a, m = self.self_attn, self.mlp
-        bsz, T, _ = x.shape
-        nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
-        cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x)
-        past = cache.length
-        if position_ids is None:
-            pos = torch.arange(past, past + T, dtype=torch.int64, device=x.device)[None]
+        if cache is not None:
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos)
         else:
-            pos = position_ids.reshape(-1, position_ids.shape[-1]) if position_ids.dim() == 1 else position_ids
-            if pos.dim() != 2 or pos.shape[1] != T or pos.shape[0] not in (1, bsz):
-                raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
-            pos = pos.to(device=x.device, dtype=torch.int64)
-        cos, sin = a._rope_table(past + T, x.device)
-        h = self.input_layernorm(x)
-        q = a.q_proj(h).view(bsz, T, nh, hd)
-        k = a.k_proj(h).view(bsz, T, nkv, hd)
-        v = a.v_proj(h).view(bsz, T, nkv, hd)
-        attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos)
+            cos, sin = a._rope_tables(position_ids, T, x.device)
+            q, k = ops.RopeFn.apply(q, cos, sin), ops.RopeFn.apply(k, cos, sin)
+            attn = self._packed_attention(q, k, v, attention_mask, 1.0 / math.sqrt(hd))
         x = a.o_proj(attn.reshape(bsz, T, self.hidden_size), residual=x)
         h = self.post_attention_layernorm(x)
         x = m.down_proj(ops.SiluMulFn.apply(m.gate_proj(h), m.up_proj(h)), residual=x)
@@ -429,40 +408,15 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         k = a.k_proj.forward_codes(hint, out_dtype=f32).view(bsz, T, nkv, hd)
         v = a.v_proj.forward_codes(hint, out_dtype=f32).view(bsz, T, nkv, hd)
         scale = 1.0 / math.sqrt(hd)
-        qr = torch.empty((bsz, T, nh, hd), dtype=cd, device=x.device)
         cache = None
         if past_key_value is not None or use_cache:
             cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x, head_bits=4)
-            past = cache.length
-            L = past + T
-            if position_ids is None:
-                pos = torch.arange(past, L, dtype=torch.int64, device=x.device)[None]
-            else:
-                pos = position_ids.reshape(-1, position_ids.shape[-1]) if position_ids.dim() == 1 else position_ids
-                if pos.dim() != 2 or pos.shape[1] != T or pos.shape[0] not in (1, bsz):
-                    raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
-                pos = pos.to(device=x.device, dtype=torch.int64)
-            if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[0] not in (1, bsz)
-                                               or tuple(attention_mask.shape[1:]) != (1, T, L)):
-                raise ValueError(f"Attention mask should be of size {(bsz, 1, T, L)}, but is {attention_mask.size()}")
-            cos, sin = a._rope_table(L, x.device)
-            cache.reserve(T)
-            kr = vr = None
-            if past == 0:
-                kr, vr = torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device), torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device)
-            ops.kv_append_quant(k, v, 4, cd, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos,
-                                sin=sin, positions=pos)
-            cache.length = L
-            if past == 0:
-                mask = attention_mask
-                if mask is not None and mask.shape[0] != bsz:
-                    mask = mask.expand(bsz, 1, T, L)
-                attn = self._packed_attention(qr, kr, vr, mask, scale)
-            else:
-                attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
+            pos = self._positions(position_ids, cache.length, bsz, T, x.device)
+            cos, sin = a._rope_table(cache.length + T, x.device)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, scale, cos, sin, pos, head_bits=4)
         else:
             cos, sin = a._rope_tables(position_ids, T, x.device)
-            kr, vr = torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device), torch.empty((bsz, T, nkv, hd), dtype=cd, device=x.device)
+            qr, kr, vr = (torch.empty(t.shape, dtype=cd, device=x.device) for t in (q, k, v))
             ops.kv_append_quant(k, v, 4, cd, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin)
             attn = self._packed_attention(qr, kr, vr, attention_mask, scale)
         x2 = a.o_proj.forward_codes(ops.act_codes(attn.reshape(bsz * T, H), 4), residual=x2, out_dtype=torch.float32)

@@ -1622,6 +1622,37 @@ class LetVectorsFn(torch.autograd.Function):
         return tuple(pg) + tuple(res[7:]) + (None,) * 8
 
 
+def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, positions):
+    """What kv_append and kv_append_quant validate alike: the caches (None: no cache) against k, the row range, q, the cos / sin
+    tables and the positions.  Returns (cap, nh, P, pos_bstride, contiguous positions)."""
+    bs, Tq, nkv, hd = k.shape
+    cap = 0
+    if k_cache is not None:
+        if v_cache is None or k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or \
+                (k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]) != (bs, nkv, hd) or k_cache.dtype != cache_dtype \
+                or v_cache.dtype != cache_dtype:
+            raise C.OQError(f"{fn}: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)} {k.dtype}")
+        cap = k_cache.shape[2]
+        if past < 0 or past + Tq > cap:
+            raise C.OQError(f"{fn}: rows [{past}, {past + Tq}) beyond the capacity {cap}")
+    nh = 0
+    if q is not None:
+        nh = q.shape[2]
+        if q.dim() != 4 or tuple(q.shape[:2]) != (bs, Tq) or q.shape[3] != hd or q.dtype != k.dtype:
+            raise C.OQError(f"{fn}: q {tuple(q.shape)} does not fit k {tuple(k.shape)}")
+    P, pbs = 0, 0
+    if cos is not None:
+        if cos.dim() != 2 or cos.shape[1] != hd or tuple(sin.shape) != tuple(cos.shape):
+            raise C.OQError(f"{fn}: cos / sin tables {tuple(cos.shape)} for head_dim {hd}")
+        P = cos.shape[0]
+        if positions is not None:
+            if positions.dim() != 2 or positions.shape[1] != Tq or positions.shape[0] not in (1, bs) or positions.dtype != torch.int64:
+                raise C.OQError(f"{fn}: positions {tuple(positions.shape)} {positions.dtype} (int64 [1 | {bs}, {Tq}])")
+            positions = positions.contiguous()
+            pbs = Tq if positions.shape[0] == bs and bs > 1 else 0
+    return cap, nh, P, pbs, positions
+
+
 def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None):
     """Append one step's k / v [bs, Tq, nkv, hd] to rows [past, past + Tq) of the [bs, nkv, cap, hd] caches in ONE launch
     (csrc/oq_decode.hip), rotating q (into q_out) and k with the cos / sin tables [P, hd] (rows = positions 0..P-1) gathered at
@@ -1630,29 +1661,10 @@ def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=
     bs, Tq, nkv, hd = k.shape
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype:
         raise C.OQError(f"kv_append: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
-    if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or (k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]) != \
-            (bs, nkv, hd) or k_cache.dtype != k.dtype or v_cache.dtype != k.dtype:
-        raise C.OQError(f"kv_append: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)} {k.dtype}")
-    cap = k_cache.shape[2]
-    if past < 0 or past + Tq > cap:
-        raise C.OQError(f"kv_append: rows [{past}, {past + Tq}) beyond the capacity {cap}")
-    nh = 0
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append", k, v, k_cache, v_cache, k.dtype, past, q, cos, sin, positions)
     if q is not None:
-        nh = q.shape[2]
-        if q.dim() != 4 or tuple(q.shape[:2]) != (bs, Tq) or q.shape[3] != hd or q.dtype != k.dtype:
-            raise C.OQError(f"kv_append: q {tuple(q.shape)} does not fit k {tuple(k.shape)}")
         q = q.contiguous()
         q_out = q if q_out is None else q_out
-    P, pbs = 0, 0
-    if cos is not None:
-        if cos.dim() != 2 or cos.shape[1] != hd or tuple(sin.shape) != tuple(cos.shape):
-            raise C.OQError(f"kv_append: cos / sin tables {tuple(cos.shape)} for head_dim {hd}")
-        P = cos.shape[0]
-        if positions is not None:
-            if positions.dim() != 2 or positions.shape[1] != Tq or positions.shape[0] not in (1, bs) or positions.dtype != torch.int64:
-                raise C.OQError(f"kv_append: positions {tuple(positions.shape)} {positions.dtype} (int64 [1 | {bs}, {Tq}])")
-            positions = positions.contiguous()
-            pbs = Tq if positions.shape[0] == bs and bs > 1 else 0
     k, v = k.contiguous(), v.contiguous()
     C.call("oq_kv_append", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out), C.ptr(k_cache), C.ptr(v_cache), C.dt(k),
            bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, C.stream())
@@ -1668,36 +1680,14 @@ def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, 
     bs, Tq, nkv, hd = k.shape
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_quant: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
-    cap = 0
-    if k_cache is not None:
-        if v_cache is None or k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or \
-                (k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]) != (bs, nkv, hd) or k_cache.dtype != out_dtype \
-                or v_cache.dtype != out_dtype:
-            raise C.OQError(f"kv_append_quant: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)}")
-        cap = k_cache.shape[2]
-        if past < 0 or past + Tq > cap:
-            raise C.OQError(f"kv_append_quant: rows [{past}, {past + Tq}) beyond the capacity {cap}")
-    for t, shp in ((k_out, k.shape), (v_out, k.shape)):
-        if t is not None and (tuple(t.shape) != tuple(shp) or t.dtype != out_dtype or not t.is_contiguous()):
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, k_cache, v_cache, out_dtype, past, q, cos, sin, positions)
+    for t in (k_out, v_out):
+        if t is not None and (tuple(t.shape) != tuple(k.shape) or t.dtype != out_dtype or not t.is_contiguous()):
             raise C.OQError("kv_append_quant: k_out / v_out must be contiguous tensors of k's shape in the output dtype")
-    nh = 0
     if q is not None:
-        nh = q.shape[2]
-        if q.dim() != 4 or tuple(q.shape[:2]) != (bs, Tq) or q.shape[3] != hd or q.dtype != k.dtype:
-            raise C.OQError(f"kv_append_quant: q {tuple(q.shape)} does not fit k {tuple(k.shape)}")
         if q_out is None or tuple(q_out.shape) != tuple(q.shape) or q_out.dtype != out_dtype:
             raise C.OQError("kv_append_quant: q_out must be a tensor of q's shape in the output dtype")
         q = q.contiguous()
-    P, pbs = 0, 0
-    if cos is not None:
-        if cos.dim() != 2 or cos.shape[1] != hd or tuple(sin.shape) != tuple(cos.shape):
-            raise C.OQError(f"kv_append_quant: cos / sin tables {tuple(cos.shape)} for head_dim {hd}")
-        P = cos.shape[0]
-        if positions is not None:
-            if positions.dim() != 2 or positions.shape[1] != Tq or positions.shape[0] not in (1, bs) or positions.dtype != torch.int64:
-                raise C.OQError(f"kv_append_quant: positions {tuple(positions.shape)} {positions.dtype} (int64 [1 | {bs}, {Tq}])")
-            positions = positions.contiguous()
-            pbs = Tq if positions.shape[0] == bs and bs > 1 else 0
     k, v = k.contiguous(), v.contiguous()
     C.call("oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache),
            C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs,

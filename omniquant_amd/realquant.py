@@ -156,18 +156,23 @@ class PackedLinear(nn.Module):
                C.fptr(vec[1]), C.fptr(vec[2]), C.stream())
         return ops.IntCodes(codes, vec[0], vec[1], vec[2], 4)
 
-    def _check_a4_input(self, x):
-        if self.act_bits != 4:
-            raise C.OQError("PackedLinear: integer-code inputs need act_bits = 4")
+    def _check_input(self, x, dtypes, what, allowed):
+        """The one input check: a GPU tensor that needs no gradient, with the layer's feature count, in one of `dtypes`
+        (`what` and `allowed` word the dtype message)."""
         if not x.is_cuda or not self.qweight.is_cuda:
             raise C.OQError("PackedLinear: the HIP path needs GPU tensors (got a CPU tensor); there is no CPU fallback")
         if torch.is_grad_enabled() and x.requires_grad:
             raise C.OQError("PackedLinear is inference-only: no gradient through a packed weight (run under torch.no_grad())")
-        if x.dtype not in (torch.bfloat16, torch.float32):
-            raise C.OQError(f"PackedLinear (act_bits 4): activation dtype {x.dtype} (float32 or bfloat16; the blocks convert "
-                            "float16 hidden states to their compute dtype on entry)")
         if x.shape[-1] != self.infeatures:
             raise C.OQError(f"PackedLinear: input has {x.shape[-1]} features, the layer {self.infeatures}")
+        if x.dtype not in dtypes:
+            raise C.OQError(f"PackedLinear{what} {x.dtype} ({allowed})")
+
+    def _check_a4_input(self, x):
+        if self.act_bits != 4:
+            raise C.OQError("PackedLinear: integer-code inputs need act_bits = 4")
+        self._check_input(x, (torch.float32, torch.bfloat16), " (act_bits 4): activation dtype",
+                          "float32 or bfloat16; the blocks convert float16 hidden states to their compute dtype on entry")
 
     def quantize_input(self, x):
         """ops.IntCodes of the per-token 4-bit quantiser applied to x [..., in] (float32 / bfloat16)."""
@@ -183,8 +188,9 @@ class PackedLinear(nn.Module):
         if out_dtype not in (torch.float32, torch.bfloat16):
             raise C.OQError(f"PackedLinear (act_bits 4): output dtype {out_dtype} (float32 or bfloat16)")
         codes = xint.codes
-        if codes.dim() != 2 or codes.shape[1] != self.infeatures or codes.dtype != torch.int8 or not codes.is_cuda:
-            raise C.OQError(f"PackedLinear.forward_codes: codes {tuple(codes.shape)} {codes.dtype} for in={self.infeatures}")
+        if codes.dim() != 2:
+            raise C.OQError(f"PackedLinear.forward_codes: codes {tuple(codes.shape)} (expected [M, {self.infeatures}])")
+        self._check_input(codes, (torch.int8,), ".forward_codes: codes dtype", "int8")
         M, K, N = codes.shape[0], self.infeatures, self.outfeatures
         res2 = None
         if residual is not None:
@@ -212,14 +218,7 @@ class PackedLinear(nn.Module):
             self._check_a4_input(x)
             y = self.forward_codes(self.quantize_input(x), residual, x.dtype)
             return y.view(*x.shape[:-1], self.outfeatures)
-        if not x.is_cuda or not self.qweight.is_cuda:
-            raise C.OQError("PackedLinear: the HIP path needs GPU tensors (got a CPU tensor); there is no CPU fallback")
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise C.OQError("PackedLinear is inference-only: no gradient through a packed weight (run under torch.no_grad())")
-        if x.shape[-1] != self.infeatures:
-            raise C.OQError(f"PackedLinear: input has {x.shape[-1]} features, the layer {self.infeatures}")
-        if x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            raise C.OQError(f"PackedLinear: activation dtype {x.dtype} (float16, bfloat16 or float32)")
+        self._check_input(x, (torch.float16, torch.bfloat16, torch.float32), ": activation dtype", "float16, bfloat16 or float32")
         K, N = self.infeatures, self.outfeatures
         x2 = x.reshape(-1, K).contiguous()
         M = x2.shape[0]
@@ -268,6 +267,12 @@ def _act_bits(qlayer):
         elif isinstance(m, QuantMatMul):
             bits += [m.x1_quantizer.n_bits, m.x2_quantizer.n_bits]
     return min(bits)
+
+
+def _replace_module(root, name, new):
+    """Put `new` where root.get_submodule(name) is."""
+    parent, _, leaf = name.rpartition(".")
+    setattr(root.get_submodule(parent), leaf, new)
 
 
 def _mark_packed(qlayer, act_bits, act_quant=False):
@@ -345,12 +350,8 @@ def pack_block(qlayer, wbits, act_quant=False):
             continue
         wq = module.weight_quantizer
         packed = pack_linear(module.weight.float(), wq.scales, wq.zeros, wbits, wq.group_size, module.bias)
-        pl = PackedLinear(wbits, wq.group_size, module.in_features, module.out_features, packed, act_bits=4 if act_quant else 16)
-        parent = qlayer
-        parts = name.split(".")
-        for p_ in parts[:-1]:
-            parent = getattr(parent, p_)
-        setattr(parent, parts[-1], pl)
+        _replace_module(qlayer, name, PackedLinear(wbits, wq.group_size, module.in_features, module.out_features, packed,
+                                                   act_bits=4 if act_quant else 16))
     _mark_packed(qlayer, act_bits, act_quant)
     return qlayer
 
@@ -367,13 +368,9 @@ def load_packed_block(qlayer, state_dict, wbits, group_size, act_quant=False):
         check_act_quant_eligible(qlayer, wbits, group_size or 0)
     for name, module in list(qlayer.named_modules()):
         if isinstance(module, QuantLinear):
-            pl = PackedLinear.empty(wbits, group_size, module.in_features, module.out_features, (name + ".bias") in state_dict,
-                                    module.weight.device, act_bits=4 if act_quant else 16)
-            parent = qlayer
-            parts = name.split(".")
-            for p_ in parts[:-1]:
-                parent = getattr(parent, p_)
-            setattr(parent, parts[-1], pl)
+            _replace_module(qlayer, name, PackedLinear.empty(wbits, group_size, module.in_features, module.out_features,
+                                                             (name + ".bias") in state_dict, module.weight.device,
+                                                             act_bits=4 if act_quant else 16))
         elif isinstance(module, (OmniLayerNorm, OmniLlamaRMSNorm)) and module.bias is None and (name + ".bias") in state_dict:
             ref = state_dict[name + ".bias"]
             del module.bias

@@ -58,3 +58,25 @@ def test_act_order_g_idx_is_refused():
 def test_unsupported_layouts_are_refused(bits, group, inn, out):
     with pytest.raises(OQError):
         PackedLinear.empty(bits, group, inn, out, False, "cpu")
+
+
+#: (in, out) -> splits of the contraction in oq_packed_gemv (float) and oq_packed_gemv_a4 (integer).  The float GEMV's split
+#: count fixes its summation order, hence its bits: the plan is part of the value contract.
+_SPLIT_PLANS = [(96, 160, 3, 3), (416, 96, 13, 13), (256, 288, 8, 8), (4096, 4096, 32, 32), (4096, 11008, 12, 12),
+                (11008, 4096, 32, 32), (8192, 1024, 128, 128), (4096, 32000, 8, 5)]
+
+
+@pytest.mark.parametrize("inn,out,fsplits,isplits", _SPLIT_PLANS)
+def test_gemv_split_plans_are_pinned(inn, out, fsplits, isplits):
+    """The exported workspace sizes (no GPU needed) pin the split plans: splits * M * out * 4 bytes of fp32 partials for the
+    float GEMV, splits * (M + 1) * out * 4 bytes of int32 partials (row M: the column code sums) for the integer one."""
+    from omniquant_amd import _capi
+    for M in (1, 16):
+        assert _capi.size_call("oq_packed_gemv_workspace", M, inn, out, 4) == fsplits * M * out * 4
+        assert _capi.size_call("oq_packed_gemv_a4_workspace", M, inn, out) == isplits * (M + 1) * out * 4
+
+
+def test_gemv_split_plan_example_sizes():
+    from omniquant_amd import _capi
+    assert _capi.size_call("oq_packed_gemv_workspace", 16, 4096, 4096, 4) == 8388608
+    assert _capi.size_call("oq_packed_gemv_a4_workspace", 16, 4096, 4096) == 8912896
