@@ -363,6 +363,23 @@ int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_
 int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
                    int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
                    int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream);
+/*   4-bit code cache (W4A4 blocks): K and V as codes uint8 [bs, nkv, cap, hd / 2] -- dim d of a row in nibble d % 8 of its
+ *      little-endian 32-bit word d / 8, i.e. byte i holds dim 2i (low nibble) and dim 2i + 1 (high nibble) -- plus meta f32
+ *      [bs, nkv, cap, 2] = (scale, rounded zero-point) per row.  A stored element's value is fp32((code - zp) * scale), bit for
+ *      bit what oq_kv_append_quant writes to an f32 cache (a row whose scale is 0, inf or NaN is NaN throughout there: codes 0
+ *      under a NaN scale here).
+ *   oq_kv_append_quant_codes: oq_kv_append_quant (nbits 4) with the code buffers as the cache destination; q_out, k_out, v_out
+ *      receive the fake-quant values in dtype as before (k_out / v_out may both be NULL).
+ *   oq_attn_decode_codes: oq_attn_decode over such a cache (same softmax, mask handling, split plan, workspace and
+ *      reproducibility; q and o in dtype).  K and V are dequantised in registers, scores as scale_k * sum q (c - zp_k). */
+int oq_kv_append_quant_codes(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                             void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq, int nh,
+                             int nkv, int hd, int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P,
+                             const int64_t* pos, int64_t pos_bstride, int nbits, void* stream);
+int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta, void* o,
+                         int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, float scale,
+                         const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* ---- fused causal attention (models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using

@@ -66,23 +66,30 @@ class QuantBlockMixin:
     def _kv_cache_in(self, past_key_value, bsz, Tq, nkv, hd, x, head_bits=None):
         """The PackedKVCache this forward appends to: a new one (prefill), the caller's (appended in place) or a copy of a
         reference-layout (k, v) tuple converted to the compute dtype (the caller's tensors are left alone).  head_bits (W4A4
-        blocks, whose cache holds head-quantised k / v): the tuple's raw rows are quantised once, on import."""
+        blocks, whose cache holds head-quantised k / v): the tuple's raw rows are quantised once, on import.
+        A block packed with kv_cache_bits=4 creates, and converts tuples into, 4-bit code caches; a caller's PackedKVCache of
+        either kind is taken as it is (an empty pre-sized code cache switches an unmarked W4A4 block to codes), except that a
+        code cache needs the head quantisers (head_bits 4)."""
         from ._capi import OQError
         from .kvcache import PackedKVCache
         if hd not in (64, 128):
             raise OQError(f"KV-cache decoding covers head_dim 64 and 128 (oq_attn_decode), not {hd}")
+        code_bits = self.__dict__["_oq_packed"].get("kv_cache_bits")
         if past_key_value is None:
-            return PackedKVCache(bsz, nkv, hd, x.dtype, x.device, Tq)
+            return PackedKVCache(bsz, nkv, hd, x.dtype, x.device, Tq, code_bits=code_bits)
         if isinstance(past_key_value, PackedKVCache):
             c = past_key_value
             if (c.bs, c.nkv, c.hd) != (bsz, nkv, hd) or c.dtype != x.dtype or c.device != x.device:
                 raise OQError(f"{c!r} does not fit this block's step: batch {bsz}, {nkv} kv heads of {hd}, {x.dtype} on {x.device}")
+            if c.code_bits is not None and head_bits != c.code_bits:
+                raise OQError(f"{c!r}: code_bits {c.code_bits} needs a W4A4 block (this block's k / v are not on a 4-bit grid)")
             return c
         if isinstance(past_key_value, (tuple, list)) and len(past_key_value) == 2:
             k = past_key_value[0]
             if not torch.is_tensor(k) or k.dim() != 4 or (k.shape[0], k.shape[1], k.shape[3]) != (bsz, nkv, hd):
                 raise OQError(f"past_key_value {tuple(getattr(k, 'shape', ()))}: expected [{bsz}, {nkv}, T, {hd}]")
-            return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq, head_bits=head_bits)
+            return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq, head_bits=head_bits,
+                                            code_bits=code_bits)
         raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
 
     @staticmethod
@@ -100,7 +107,9 @@ class QuantBlockMixin:
         by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
         (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation.
         head_bits (W4A4 blocks): q / k / v (float32 or the cache's dtype) also pass the per-(token, head) quantiser of that
-        width in the append's launch, so the cache holds, and the attention reads, the quantised values in the cache's dtype."""
+        width in the append's launch, so the cache holds, and the attention reads, the quantised values in the cache's dtype.
+        A code cache (cache.code_bits 4) receives the codes instead (oq_kv_append_quant_codes) and steps with a past run
+        oq_attn_decode_codes on them; its prefill runs the same attention launches on the same q / k / v values."""
         from . import ops
         bsz, Tq = q.shape[0], q.shape[1]
         past = cache.length
@@ -119,14 +128,20 @@ class QuantBlockMixin:
         else:
             qr = torch.empty(q.shape, dtype=cache.dtype, device=q.device)
             kr, vr = (torch.empty(k.shape, dtype=cache.dtype, device=q.device) for _ in range(2)) if past == 0 else (None, None)
-            ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr, k_out=kr,
-                                v_out=vr, cos=cos, sin=sin, positions=positions)
+            if cache.code_bits is not None:
+                ops.kv_append_codes(k, v, cache.dtype, cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta, past=past, q=q,
+                                    q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions)
+            else:
+                ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr,
+                                    k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions)
         cache.length = L
         if past == 0:
             mask = attention_mask
             if mask is not None and mask.shape[0] != bsz:
                 mask = mask.expand(bsz, 1, Tq, L)
             return self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
+        if cache.code_bits is not None:
+            return ops.decode_attention_codes(qr, cache, L, scale, attention_mask)
         return ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
 
     @staticmethod

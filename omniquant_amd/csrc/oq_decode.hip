@@ -1,6 +1,7 @@
 // Incremental-decoding kernels of the packed (real-quant) blocks on gfx950: the KV-cache append with RoPE at arbitrary
-// positions (one kernel template; its QUANT instantiations add the W4A4 head quantisers and serve oq_kv_append_quant), and
-// attention of 1..Tq query rows against the cached K/V.
+// positions (one kernel template; its QUANT instantiations add the W4A4 head quantisers and serve oq_kv_append_quant, its
+// CODES instantiations also store the 4-bit codes: oq_kv_append_quant_codes), and attention of 1..Tq query rows against
+// the cached K/V, held as floats (oq_attn_decode) or as 4-bit codes (oq_attn_decode_codes).
 // Reference lines: models/int_llama_layer.py:121-135,177 (rotary embedding gathered at position_ids, torch.cat with
 // past_key_value, present_key_value) and :143-163 (scores, mask, softmax, PV); models/int_opt_layer.py:110-121,151-170.
 //
@@ -34,9 +35,13 @@ struct AppendP {
     int64_t pos_bs;
     int nbits;
     float inv_q;
+    // code destination (CODES instantiations, 4-bit): rows of hd / 2 bytes, dim d in nibble d % 8 of the little-endian
+    // 32-bit word d / 8, and one (scale, rounded zero-point) pair per row; value = (code - zp) * scale
+    uint8_t *k_codes, *v_codes;
+    float *k_meta, *v_meta;
 };
 
-template <typename TIN, typename T, bool QUANT>
+template <typename TIN, typename T, bool QUANT, bool CODES>
 __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     const int hd = p.hd, nh = p.nh, nkv = p.nkv;
     const int64_t Tq = p.Tq, cap = p.cap, past = p.past;
@@ -56,6 +61,8 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
         const TIN* src;
         T* dst;
         T* dst2;
+        uint8_t* cdst = nullptr;
+        float* mdst = nullptr;
         bool rot = p.cs != nullptr;
         if (slot < nh) {
             src = q + ((b * Tq + t) * nh + slot) * hd;
@@ -66,11 +73,19 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
             src = k + ((b * Tq + t) * nkv + h) * hd;
             dst = kc ? kc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
             dst2 = k_out ? k_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
+            if constexpr (CODES) {
+                cdst = p.k_codes + ((b * nkv + h) * cap + past + t) * half;
+                mdst = p.k_meta + ((b * nkv + h) * cap + past + t) * 2;
+            }
         } else {
             const int h = slot - nh - nkv;
             src = v + ((b * Tq + t) * nkv + h) * hd;
             dst = vc ? vc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
             dst2 = v_out ? v_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
+            if constexpr (CODES) {
+                cdst = p.v_codes + ((b * nkv + h) * cap + past + t) * half;
+                mdst = p.v_meta + ((b * nkv + h) * cap + past + t) * 2;
+            }
             rot = false;
         }
         float a[8], c[8];
@@ -104,18 +119,40 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
             if (bad != 0.f) { hi = NAN; lo = NAN; }
             float inv_s = 0.f;
             const QP qp = make_qp(hi, lo, false, 0.f, 0.f, p.nbits, 0, p.inv_q, &inv_s);
-            const bool regular = qp.s != 0.f && fabsf(qp.s) <= 3.4028234663852886e38f && bad == 0.f;
+            // (a subnormal scale whose reciprocal overflows takes the exact-division branch too: x * inf would turn a zero
+            // element into NaN)
+            const bool regular = qp.s != 0.f && fabsf(qp.s) <= 3.4028234663852886e38f && bad == 0.f &&
+                                 fabsf(inv_s) <= 3.4028234663852886e38f;
+            uint32_t wa = 0, wc = 0;            // CODES: the lane's two words of 8 codes
+            float nan_row = 0.f;                // CODES: an element of the row came out as NaN
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float& x = i < 8 ? a[i] : c[i - 8];
                 if (regular) {
                     float tq;
                     const float rq = rne_div(x, qp.s, inv_s, &tq);
-                    x = (__builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q) - qp.z) * qp.s;
+                    const float code = __builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q);
+                    x = (code - qp.z) * qp.s;
+                    if constexpr (CODES) (i < 8 ? wa : wc) |= (uint32_t)code << (4 * (i & 7));
                 } else {
                     float u = rne_ste(x / qp.s) + qp.z;
                     u = (u != u) ? u : fminf(fmaxf(u, 0.f), Q);
                     x = (u - qp.z) * qp.s;
+                    if constexpr (CODES) {
+                        if (u != u) nan_row = 1.f;
+                        else (i < 8 ? wa : wc) |= (uint32_t)u << (4 * (i & 7));
+                    }
+                }
+            }
+            if constexpr (CODES) {
+                // a row of scale 0, inf or NaN (constant rows, overflowing ranges, NaN inputs) comes out of the branch above as
+                // NaN in every element: codes 0 under a NaN scale hold exactly that.  Every other row has no NaN at all.
+                nan_row = wave_max(nan_row, hv);
+                if (cdst) {
+                    uint32_t* w = reinterpret_cast<uint32_t*>(cdst);
+                    w[d0 / 8] = nan_row != 0.f ? 0u : wa;
+                    w[(half + d0) / 8] = nan_row != 0.f ? 0u : wc;
+                    if (d0 == 0) *reinterpret_cast<f32x2*>(mdst) = f32x2{nan_row != 0.f ? NAN : qp.s, qp.z};
                 }
             }
         }
@@ -130,33 +167,33 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     }
 }
 
-template <typename TIN, typename T, bool QUANT>
+template <typename TIN, typename T, bool QUANT, bool CODES>
 void launch_append(const AppendP& p, hipStream_t st) {
     const int64_t n = p.bs * p.Tq * (p.nh + 2 * p.nkv) * (p.hd / 16);
     const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT>), dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT, CODES>), dim3(grid), dim3(256), 0, st, p);
 }
 
 // The checks, the grid and the dtype dispatch both ABI entry points share (fn: the entry point's name for the messages).
 // The caller has checked what is its own: which pointers it requires, head_dim, nbits and the dtype pairs it admits.
-template <bool QUANT>
+template <bool QUANT, bool CODES = false>
 int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* stream) {
     OQ_CHECK_ARG(!p.q || p.q_out, "%s: q without q_out", fn);
     OQ_CHECK_ARG(p.bs > 0 && p.Tq > 0 && p.nkv > 0 && p.nh >= 0 && (p.q || p.nh == 0), "%s: bad shape", fn);
-    OQ_CHECK_ARG(!p.kc || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
+    OQ_CHECK_ARG(!(p.kc || p.k_codes) || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
                  (long long)p.past, (long long)(p.past + p.Tq), (long long)p.cap);
     OQ_CHECK_ARG(!p.cs == !p.sn, "%s: cos and sin go together", fn);
     OQ_CHECK_ARG(!p.cs || (p.P > 0 && oq_aligned16(p.cs) && oq_aligned16(p.sn)), "%s: cos/sin tables must be 16-byte aligned, P > 0", fn);
     OQ_CHECK_ARG(p.pos_bs >= 0, "%s: pos_bstride", fn);
-    const void* ptrs[] = {p.q, p.k, p.v, p.q_out, p.k_out, p.v_out, p.kc, p.vc};
+    const void* ptrs[] = {p.q, p.k, p.v, p.q_out, p.k_out, p.v_out, p.kc, p.vc, p.k_codes, p.v_codes, p.k_meta, p.v_meta};
     for (const void* ptr : ptrs) OQ_CHECK_ARG(!ptr || oq_aligned16(ptr), "%s: tensors must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == OQ_F32 && in_dtype == OQ_F32) {
-        launch_append<float, float, QUANT>(p, st);
+        launch_append<float, float, QUANT, CODES>(p, st);
     } else if (dtype == OQ_BF16 && in_dtype == OQ_BF16) {
-        launch_append<bf16_t, bf16_t, QUANT>(p, st);
+        launch_append<bf16_t, bf16_t, QUANT, CODES>(p, st);
     } else if constexpr (QUANT) {
-        launch_append<float, bf16_t, true>(p, st);       // f32 -> bf16: the only other pair the quantising entry admits
+        launch_append<float, bf16_t, true, CODES>(p, st);       // f32 -> bf16: the only other pair the quantising entry admits
     } else {
         oq_set_error("%s: dtype %d unsupported", fn, dtype);
         return OQ_E_UNSUPPORTED;
@@ -188,14 +225,84 @@ __device__ __forceinline__ float ld_mask(const void* m, int mdt, int64_t i) {
     return (float)reinterpret_cast<const f16_t*>(m)[i];
 }
 
-// Split kernel: grid (ns, nkv, bs).  Lane group `grp` (hd/8 lanes) handles rows j0 + grp, j0 + grp + G, ... of the split,
+// ---- where the cached rows come from: the kernel's K / V argument and its per-row loads ---------------------------------
+// A policy gives DPL (dims of a row one lane holds; HD / DPL lanes make a lane group), SCALED (a row carries a scale that
+// multiplies its score and its probability once per row), at(row0, d0) (the lane's view of one (b, kv head)), load(k, v, j)
+// of row j into Row registers, and Row::unpack / Row::scale.
+template <typename T, int HD>
+struct FloatKV {                        // [bs, nkv, cap, HD] of T: 16-byte loads, 8 dims per lane
+    static constexpr int DPL = 8;
+    static constexpr bool SCALED = false;
+    const T *k, *v;
+    struct Row {
+        Raw8<T> r;
+        __device__ __forceinline__ void unpack(float (&o)[8]) const { r.unpack(o); }
+        __device__ __forceinline__ float scale() const { return 1.f; }
+    };
+    __device__ __forceinline__ FloatKV at(int64_t row0, int d0) const { return {k + row0 * HD + d0, v + row0 * HD + d0}; }
+    __device__ __forceinline__ void load(Row& kr, Row& vr, int64_t j) const {
+        kr.r.load(k + j * HD);
+        vr.r.load(v + j * HD);
+    }
+};
+
+// 4-bit code cache: rows of HD / 2 code bytes (dim d in nibble d % 8 of word d / 8) plus one (scale, zero-point) pair, value
+// = (code - zp) * scale.  A lane holds DPL dims: DPL / 8 words, one 4- or 8-byte load.  unpack gives code - zp (exact: small
+// integers held in floats, or a NaN zero-point); the scale is applied per row, so scores are s_k * sum q (c - z_k) and the PV
+// term (p s_v) (c - z_v).
+template <int HD, int DPL_>
+struct CodeKV {
+    static constexpr int DPL = DPL_;
+    static constexpr bool SCALED = true;
+    static constexpr int W = DPL / 8;
+    const uint8_t *k, *v;
+    const f32x2 *km, *vm;
+    struct Row {
+        uint32_t w[W];
+        f32x2 m;
+        __device__ __forceinline__ void load(const uint8_t* p) {
+            if constexpr (W == 2) {
+                typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+                const u32x2 r = *reinterpret_cast<const u32x2*>(p);
+                w[0] = r[0];
+                w[1] = r[1];
+            } else {
+                w[0] = *reinterpret_cast<const uint32_t*>(p);
+            }
+        }
+        __device__ __forceinline__ void unpack(float (&o)[DPL]) const {
+#pragma unroll
+            for (int n = 0; n < W; ++n) {
+                const uint32_t lo = w[n] & 0x0F0F0F0Fu, hi = (w[n] >> 4) & 0x0F0F0F0Fu;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    o[8 * n + 2 * i] = (float)((lo >> (8 * i)) & 0xFFu) - m[1];          // v_cvt_f32_ubyte<i>
+                    o[8 * n + 2 * i + 1] = (float)((hi >> (8 * i)) & 0xFFu) - m[1];
+                }
+            }
+        }
+        __device__ __forceinline__ float scale() const { return m[0]; }
+    };
+    __device__ __forceinline__ CodeKV at(int64_t row0, int d0) const {
+        return {k + row0 * (HD / 2) + d0 / 2, v + row0 * (HD / 2) + d0 / 2, km + row0, vm + row0};
+    }
+    __device__ __forceinline__ void load(Row& kr, Row& vr, int64_t j) const {
+        kr.load(k + j * (HD / 2));
+        vr.load(v + j * (HD / 2));
+        kr.m = km[j];
+        vr.m = vm[j];
+    }
+};
+
+// Split kernel: grid (ns, nkv, bs).  Lane group `grp` (HD / DPL lanes) handles rows j0 + grp, j0 + grp + G, ... of the split,
 // U rows in flight; query rows are processed QB at a time (rows r = t*rep + i of this kv head).  Workspace per
 // (b, kv head, split, r): [m, l, acc[HD]] with m in the log2 domain.
-template <typename T, int HD, int QB>
-__global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, const T* kc, const T* vc, float* ws, int64_t Tq,
-                                                                  int nh, int nkv, int64_t cap, int64_t L, float scale,
-                                                                  const void* mask, int mdt, int64_t m_bs, int64_t m_ld, int ns) {
-    constexpr int LPK = HD / 8;
+template <typename T, int HD, int QB, typename KV>
+__global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, const KV kv_all, float* ws, int64_t Tq, int nh,
+                                                                  int nkv, int64_t cap, int64_t L, float scale, const void* mask,
+                                                                  int mdt, int64_t m_bs, int64_t m_ld, int ns) {
+    constexpr int DPL = KV::DPL;
+    constexpr int LPK = HD / DPL;
     constexpr int GPW = 64 / LPK;
     constexpr int G = GPW * (DEC_THREADS / 64);
     constexpr int U = QB >= 8 ? 2 : 4;
@@ -206,59 +313,63 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
     const int split = blockIdx.x, kvh = blockIdx.y;
     const int64_t b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int grp = (tid >> 6) * GPW + lane / LPK, d0 = (lane % LPK) * 8;
+    const int grp = (tid >> 6) * GPW + lane / LPK, d0 = (lane % LPK) * DPL;
     const int rep = nh / nkv;
     const int64_t R = (int64_t)rep * Tq;
     const int64_t chunk = (L + ns - 1) / ns;
     const int64_t j0 = split * chunk, j1 = (j0 + chunk < L) ? j0 + chunk : L;
-    const T* kb = kc + (b * nkv + kvh) * cap * HD + d0;
-    const T* vb = vc + (b * nkv + kvh) * cap * HD + d0;
+    const KV kv = kv_all.at((b * nkv + kvh) * cap, d0);
     float* wsb = ws + ((b * nkv + kvh) * ns + split) * R * (HD + 2);
     const float zs = scale * log2e;
 
     for (int64_t r0 = 0; r0 < R; r0 += QB) {
-        float qv[QB][8], m[QB], l[QB], acc[QB][8];
+        float qv[QB][DPL], m[QB], l[QB], acc[QB][DPL];
         int64_t moff[QB];
 #pragma unroll
         for (int rr = 0; rr < QB; ++rr) {
             const int64_t r = r0 + rr < R ? r0 + rr : R - 1;        // padding rows repeat the last one (never stored)
             const int64_t t = r / rep;
-            Vec8<T>::load(q + ((b * Tq + t) * nh + (int64_t)kvh * rep + (r % rep)) * HD + d0, qv[rr]);
+            const T* qp = q + ((b * Tq + t) * nh + (int64_t)kvh * rep + (r % rep)) * HD + d0;
+#pragma unroll
+            for (int n = 0; n < DPL / 8; ++n) {
+                float t8[8];
+                Vec8<T>::load(qp + 8 * n, t8);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) qv[rr][8 * n + i] = t8[i];
+            }
             moff[rr] = b * m_bs + t * m_ld;
             m[rr] = -INFINITY;
             l[rr] = 0.f;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) acc[rr][i] = 0.f;
+            for (int i = 0; i < DPL; ++i) acc[rr][i] = 0.f;
         }
         // the trip count is uniform over the workgroup; rows past j1 are masked per lane group (and never loaded)
         for (int64_t jb = j0; jb < j1; jb += (int64_t)G * U) {
-            Raw8<T> kr[U], vr[U];
+            typename KV::Row kr[U], vr[U];
             bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t j = jb + u * G + grp;
                 ok[u] = j < j1;
-                if (ok[u]) {
-                    kr[u].load(kb + j * HD);
-                    vr[u].load(vb + j * HD);
-                }
+                if (ok[u]) kv.load(kr[u], vr[u], j);
             }
             float z[U][QB];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                float kf[8];
+                float kf[DPL];
                 if (ok[u]) kr[u].unpack(kf);
                 else {
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) kf[i] = 0.f;
+                    for (int i = 0; i < DPL; ++i) kf[i] = 0.f;
                 }
                 const int64_t j = jb + u * G + grp;
 #pragma unroll
                 for (int rr = 0; rr < QB; ++rr) {
                     float s = 0.f;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) s = __builtin_fmaf(qv[rr][i], kf[i], s);
+                    for (int i = 0; i < DPL; ++i) s = __builtin_fmaf(qv[rr][i], kf[i], s);
                     s = wave_sum(s, LPK);                       // every lane of the group holds q . k_j
+                    if constexpr (KV::SCALED) s *= ok[u] ? kr[u].scale() : 0.f;
                     float zz;
                     if (mask) {
                         const float mv = ok[u] ? ld_mask(mask, mdt, moff[rr] + j) : 0.f;
@@ -279,23 +390,25 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
                 m[rr] = mx;
                 l[rr] *= c;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) acc[rr][i] *= c;
+                for (int i = 0; i < DPL; ++i) acc[rr][i] *= c;
 #pragma unroll
                 for (int u = 0; u < U; ++u) z[u][rr] = ok[u] ? __builtin_amdgcn_exp2f(z[u][rr] - mx) : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                float vf[8];
+                float vf[DPL];
                 if (ok[u]) vr[u].unpack(vf);
                 else {
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) vf[i] = 0.f;
+                    for (int i = 0; i < DPL; ++i) vf[i] = 0.f;
                 }
 #pragma unroll
                 for (int rr = 0; rr < QB; ++rr) {
                     l[rr] += z[u][rr];
+                    float pw = z[u][rr];
+                    if constexpr (KV::SCALED) pw *= ok[u] ? vr[u].scale() : 0.f;
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[rr][i] = __builtin_fmaf(z[u][rr], vf[i], acc[rr][i]);
+                    for (int i = 0; i < DPL; ++i) acc[rr][i] = __builtin_fmaf(pw, vf[i], acc[rr][i]);
                 }
             }
         }
@@ -310,7 +423,7 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
             for (int g = 0; g < G; ++g) M = fmaxf(M, red_m[g]);
             const float w = m[rr] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[rr] - M);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) red_acc[grp][d0 + i] = acc[rr][i] * w;
+            for (int i = 0; i < DPL; ++i) red_acc[grp][d0 + i] = acc[rr][i] * w;
             if (lane % LPK == 0) red_l[grp] = l[rr] * w;
             __syncthreads();
             float* wr = wsb + r * (HD + 2);
@@ -353,25 +466,50 @@ __global__ void __launch_bounds__(HD) attn_decode_combine_kernel(const float* ws
     st1(o + ((b * Tq + t) * nh + kvh * rep + (r % rep)) * HD + tid, a / l);
 }
 
-template <typename T, int HD, int QB>
-void launch_decode(const void* q, const void* kc, const void* vc, void* o, float* ws, int64_t bs, int64_t Tq, int nh, int nkv,
-                   int64_t cap, int64_t L, float scale, const void* mask, int mdt, int64_t m_bs, int64_t m_ld, int ns,
-                   hipStream_t st) {
-    hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB>), dim3(ns, nkv, bs), dim3(DEC_THREADS), 0, st, (const T*)q, (const T*)kc,
-                       (const T*)vc, ws, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns);
-    const int64_t rows = bs * (int64_t)nh * Tq;
-    hipLaunchKernelGGL((attn_decode_combine_kernel<T, HD>), dim3(rows), dim3(HD), 0, st, (const float*)ws, (T*)o, Tq, nh, nkv, ns);
+struct DecP {
+    const void* q;
+    void* o;
+    float* ws;
+    int64_t bs, Tq;
+    int nh, nkv;
+    int64_t cap, L;
+    float scale;
+    const void* mask;
+    int mdt;
+    int64_t m_bs, m_ld;
+    int ns;
+};
+
+template <typename T, int HD, int QB, typename KV>
+void launch_decode(const DecP& p, const KV& kv, hipStream_t st) {
+    hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV>), dim3(p.ns, p.nkv, p.bs), dim3(DEC_THREADS), 0, st, (const T*)p.q, kv,
+                       p.ws, p.Tq, p.nh, p.nkv, p.cap, p.L, p.scale, p.mask, p.mdt, p.m_bs, p.m_ld, p.ns);
+    const int64_t rows = p.bs * (int64_t)p.nh * p.Tq;
+    hipLaunchKernelGGL((attn_decode_combine_kernel<T, HD>), dim3(rows), dim3(HD), 0, st, (const float*)p.ws, (T*)p.o, p.Tq, p.nh,
+                       p.nkv, p.ns);
 }
 
 template <typename T, int HD>
-void launch_decode_qb(int qb, const void* q, const void* kc, const void* vc, void* o, float* ws, int64_t bs, int64_t Tq, int nh,
-                      int nkv, int64_t cap, int64_t L, float scale, const void* mask, int mdt, int64_t m_bs, int64_t m_ld,
-                      int ns, hipStream_t st) {
+void launch_decode_float(int qb, const DecP& p, const void* kc, const void* vc, hipStream_t st) {
+    const FloatKV<T, HD> kv{(const T*)kc, (const T*)vc};
     switch (qb) {
-        case 1: launch_decode<T, HD, 1>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
-        case 2: launch_decode<T, HD, 2>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
-        case 4: launch_decode<T, HD, 4>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
-        default: launch_decode<T, HD, 8>(q, kc, vc, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mdt, m_bs, m_ld, ns, st); break;
+        case 1: launch_decode<T, HD, 1>(p, kv, st); break;
+        case 2: launch_decode<T, HD, 2>(p, kv, st); break;
+        case 4: launch_decode<T, HD, 4>(p, kv, st); break;
+        default: launch_decode<T, HD, 8>(p, kv, st); break;
+    }
+}
+
+// One or two query rows per pass leave the registers for 16 dims per lane (8-byte loads); four or eight keep 8 dims.
+template <typename T, int HD>
+void launch_decode_codes(int qb, const DecP& p, const void* kc, const void* vc, const float* km, const float* vm, hipStream_t st) {
+    const CodeKV<HD, 16> wide{(const uint8_t*)kc, (const uint8_t*)vc, (const f32x2*)km, (const f32x2*)vm};
+    const CodeKV<HD, 8> narrow{wide.k, wide.v, wide.km, wide.vm};
+    switch (qb) {
+        case 1: launch_decode<T, HD, 1>(p, wide, st); break;
+        case 2: launch_decode<T, HD, 2>(p, wide, st); break;
+        case 4: launch_decode<T, HD, 4>(p, narrow, st); break;
+        default: launch_decode<T, HD, 8>(p, narrow, st); break;
     }
 }
 
@@ -408,16 +546,15 @@ extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_
                  "oq_attn_decode: q, o, caches and workspace must be 16-byte aligned");
     const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
     OQ_CHECK_ARG(workspace_bytes >= need, "oq_attn_decode: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-    const int ns = dec_splits(bs, nkv, L);
     const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
-    float* ws = (float*)workspace;
+    const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L)};
     hipStream_t st = (hipStream_t)stream;
     if (dtype == OQ_F32) {
-        if (hd == 64) launch_decode_qb<float, 64>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
-        else launch_decode_qb<float, 128>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+        if (hd == 64) launch_decode_float<float, 64>(qb, p, k_cache, v_cache, st);
+        else launch_decode_float<float, 128>(qb, p, k_cache, v_cache, st);
     } else if (dtype == OQ_BF16) {
-        if (hd == 64) launch_decode_qb<bf16_t, 64>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
-        else launch_decode_qb<bf16_t, 128>(qb, q, k_cache, v_cache, o, ws, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, ns, st);
+        if (hd == 64) launch_decode_float<bf16_t, 64>(qb, p, k_cache, v_cache, st);
+        else launch_decode_float<bf16_t, 128>(qb, p, k_cache, v_cache, st);
     } else {
         oq_set_error("oq_attn_decode: dtype %d unsupported", dtype);
         return OQ_E_UNSUPPORTED;
@@ -441,4 +578,57 @@ extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, i
     const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
                     nbits, 1.0f / (float)((1 << nbits) - 1)};
     return kv_append<true>("oq_kv_append_quant", p, in_dtype, dtype, stream);
+}
+
+extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                        void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype,
+                                        int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
+                                        const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                                        int nbits, void* stream) {
+    OQ_CHECK_ARG(k && v && k_codes && v_codes && k_meta && v_meta, "oq_kv_append_quant_codes: null pointer");
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_kv_append_quant_codes: head_dim %d (64 or 128)", hd);
+    OQ_CHECK_ARG(nbits == 4, "oq_kv_append_quant_codes: %d-bit codes (4)", nbits);
+    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "oq_kv_append_quant_codes: dtype %d (f32 or bf16)", dtype);
+    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "oq_kv_append_quant_codes: input dtype %d (f32 or the output dtype)",
+                 in_dtype);
+    OQ_CHECK_ARG(!k_out == !v_out, "oq_kv_append_quant_codes: k_out and v_out go together");
+    const AppendP p{q, k, v, q_out, k_out, v_out, nullptr, nullptr, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
+                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta};
+    return kv_append<true, true>("oq_kv_append_quant_codes", p, in_dtype, dtype, stream);
+}
+
+extern "C" int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                    const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                    int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
+                                    int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
+    OQ_CHECK_ARG(q && k_codes && v_codes && k_meta && v_meta && o && workspace, "oq_attn_decode_codes: null pointer");
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_attn_decode_codes: head_dim %d (64 or 128)", hd);
+    OQ_CHECK_ARG(bs > 0 && bs <= 65535 && nkv > 0 && nkv <= 65535 && nh > 0 && nh % nkv == 0,
+                 "oq_attn_decode_codes: bad heads %d / %d or batch %lld", nh, nkv, (long long)bs);
+    OQ_CHECK_ARG(Tq > 0 && L >= Tq && L <= cap, "oq_attn_decode_codes: need 1 <= Tq (%lld) <= L (%lld) <= cap (%lld)",
+                 (long long)Tq, (long long)L, (long long)cap);
+    OQ_CHECK_ARG(!mask || mask_dtype == OQ_F32 || mask_dtype == OQ_F16 || mask_dtype == OQ_BF16,
+                 "oq_attn_decode_codes: mask dtype %d", mask_dtype);
+    OQ_CHECK_ARG(mask_bstride >= 0 && mask_ld >= 0, "oq_attn_decode_codes: negative mask strides");
+    OQ_CHECK_ARG(oq_aligned16(q) && oq_aligned16(k_codes) && oq_aligned16(v_codes) && oq_aligned16(k_meta) && oq_aligned16(v_meta) &&
+                     oq_aligned16(o) && oq_aligned16(workspace),
+                 "oq_attn_decode_codes: q, o, codes, meta and workspace must be 16-byte aligned");
+    const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
+    OQ_CHECK_ARG(workspace_bytes >= need, "oq_attn_decode_codes: workspace %lld < %lld bytes", (long long)workspace_bytes,
+                 (long long)need);
+    const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
+    const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L)};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == OQ_F32) {
+        if (hd == 64) launch_decode_codes<float, 64>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
+        else launch_decode_codes<float, 128>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
+    } else if (dtype == OQ_BF16) {
+        if (hd == 64) launch_decode_codes<bf16_t, 64>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
+        else launch_decode_codes<bf16_t, 128>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
+    } else {
+        oq_set_error("oq_attn_decode_codes: dtype %d unsupported", dtype);
+        return OQ_E_UNSUPPORTED;
+    }
+    OQ_CHECK_LAUNCH("oq_attn_decode_codes");
+    return OQ_OK;
 }

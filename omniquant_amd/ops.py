@@ -1671,6 +1671,54 @@ def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=
     return q_out
 
 
+def _kv_quant_outs(fn, q, k, v, out_dtype, q_out, k_out, v_out):
+    """What the quantising appends validate alike: the destinations of the fake-quant values.  Returns contiguous (q, k, v)."""
+    for t in (k_out, v_out):
+        if t is not None and (tuple(t.shape) != tuple(k.shape) or t.dtype != out_dtype or not t.is_contiguous()):
+            raise C.OQError(f"{fn}: k_out / v_out must be contiguous tensors of k's shape in the output dtype")
+    if q is not None:
+        if q_out is None or tuple(q_out.shape) != tuple(q.shape) or q_out.dtype != out_dtype:
+            raise C.OQError(f"{fn}: q_out must be a tensor of q's shape in the output dtype")
+        q = q.contiguous()
+    return q, k.contiguous(), v.contiguous()
+
+
+def _code_buffers(fn, k_codes, v_codes, k_meta, v_meta, bs, nkv, hd):
+    """Validate the four buffers of a 4-bit code cache (kvcache.PackedKVCache(code_bits=4)); returns the capacity."""
+    if hd not in (64, 128):
+        raise C.OQError(f"{fn}: head_dim {hd} (a code cache covers 64 and 128)")
+    if k_codes.dim() != 4 or (k_codes.shape[0], k_codes.shape[1], k_codes.shape[3]) != (bs, nkv, hd // 2):
+        raise C.OQError(f"{fn}: codes {tuple(k_codes.shape)} (expected [{bs}, {nkv}, cap, {hd // 2}])")
+    cap = k_codes.shape[2]
+    for t, tail, dtype in ((k_codes, hd // 2, torch.uint8), (v_codes, hd // 2, torch.uint8), (k_meta, 2, torch.float32),
+                           (v_meta, 2, torch.float32)):
+        if tuple(t.shape) != (bs, nkv, cap, tail) or t.dtype != dtype:
+            raise C.OQError(f"{fn}: code-cache buffer {tuple(t.shape)} {t.dtype} (expected {(bs, nkv, cap, tail)} {dtype})")
+    return cap
+
+
+def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q=None, q_out=None, k_out=None, v_out=None,
+                    cos=None, sin=None, positions=None):
+    """kv_append_quant on the 4-bit grid with a code cache as the destination (csrc/oq_decode.hip, oq_kv_append_quant_codes):
+    rows [past, past + Tq) of k_codes / v_codes (uint8 [bs, nkv, cap, hd // 2]) receive the quantiser's codes and k_meta /
+    v_meta (float32 [bs, nkv, cap, 2]) its (scale, zero-point); (code - zp) * scale is, bit for bit, what kv_append_quant
+    writes to a float32 cache.  q_out / k_out / v_out receive the fake-quant values in out_dtype as they do there."""
+    bs, Tq, nkv, hd = k.shape
+    if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
+        raise C.OQError(f"kv_append_codes: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
+    _, nh, P, pbs, positions = _kv_append_args("kv_append_codes", k, v, None, None, out_dtype, past, q, cos, sin, positions)
+    cap = _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd)
+    if past < 0 or past + Tq > cap:
+        raise C.OQError(f"kv_append_codes: rows [{past}, {past + Tq}) beyond the capacity {cap}")
+    if (k_out is None) != (v_out is None):
+        raise C.OQError("kv_append_codes: k_out and v_out go together")
+    q, k, v = _kv_quant_outs("kv_append_codes", q, k, v, out_dtype, q_out, k_out, v_out)
+    C.call("oq_kv_append_quant_codes", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
+           C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past),
+           C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4, C.stream())
+    return q_out
+
+
 def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, q=None, q_out=None, k_out=None, v_out=None,
                     cos=None, sin=None, positions=None):
     """kv_append for the W4A4 packed blocks (csrc/oq_decode.hip, oq_kv_append_quant): q / k / v [bs, Tq, heads, hd] in float32
@@ -1681,14 +1729,7 @@ def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, 
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_quant: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
     cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, k_cache, v_cache, out_dtype, past, q, cos, sin, positions)
-    for t in (k_out, v_out):
-        if t is not None and (tuple(t.shape) != tuple(k.shape) or t.dtype != out_dtype or not t.is_contiguous()):
-            raise C.OQError("kv_append_quant: k_out / v_out must be contiguous tensors of k's shape in the output dtype")
-    if q is not None:
-        if q_out is None or tuple(q_out.shape) != tuple(q.shape) or q_out.dtype != out_dtype:
-            raise C.OQError("kv_append_quant: q_out must be a tensor of q's shape in the output dtype")
-        q = q.contiguous()
-    k, v = k.contiguous(), v.contiguous()
+    q, k, v = _kv_quant_outs("kv_append_quant", q, k, v, out_dtype, q_out, k_out, v_out)
     C.call("oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache),
            C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs,
            int(nbits), C.stream())
@@ -1711,6 +1752,42 @@ def act_codes(x2, nbits, out=None):
     return IntCodes(codes, vec[0], vec[1], vec[2], int(nbits))
 
 
+def _decode_mask(fn, mask, bs, Tq, L):
+    """The additive mask of a decode attention as (tensor kept alive, pointer, dtype, batch stride, row stride)."""
+    if mask is None:
+        return None, None, 0, 0, 0
+    if mask.dim() != 4 or mask.shape[1] != 1 or tuple(mask.shape[2:]) != (Tq, L) or mask.shape[0] not in (1, bs):
+        raise C.OQError(f"{fn}: mask {tuple(mask.shape)} (expected [{bs} | 1, 1, {Tq}, {L}])")
+    if mask.stride(3) != 1:
+        mask = mask.contiguous()
+    return (mask, C.ptr(mask[:1, :1, :1, :1]), C.dt(mask), mask.stride(0) if mask.shape[0] == bs and bs > 1 else 0,
+            mask.stride(2) if Tq > 1 else 0)
+
+
+def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=None):
+    """decode_attention over a 4-bit code cache (csrc/oq_decode.hip, oq_attn_decode_codes): `cache` is a PackedKVCache with
+    code_bits 4 or the (k_codes, v_codes, k_meta, v_meta) buffers; K and V are dequantised in registers as (code - zp) * scale.
+    Same scores, softmax, mask handling, split plan and reproducibility as decode_attention; q and o in the compute dtype."""
+    bs, Tq, nh, hd = q.shape
+    bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
+    if len(bufs) != 4 or bufs[0].dim() != 4 or bufs[0].shape[0] != bs:
+        raise C.OQError(f"decode_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
+    nkv = bufs[0].shape[1]
+    cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd)
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise C.OQError(f"decode_attention_codes: q {q.dtype} (float32 or bfloat16)")
+    q = q.contiguous()
+    mask, mptr, mdt, mbs, mld = _decode_mask("decode_attention_codes", mask, bs, Tq, L)
+    ws_n = C.size_call("oq_attn_decode_workspace", bs, nh, nkv, Tq, int(L), hd)
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
+        workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty_like(q) if out is None else out
+    C.call("oq_attn_decode_codes", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
+           bs, Tq, nh, nkv, hd, cap, int(L), float(scale), mptr, mdt, mbs, mld, C.ptr(workspace),
+           workspace.numel() * workspace.element_size(), C.stream())
+    return o
+
+
 def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None):
     """o [bs, Tq, nh, hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over the first L rows of the [bs, nkv, cap, hd]
     caches (csrc/oq_decode.hip: split-L streaming, fp32 online softmax, one rounding).  mask: None or additive [bs | 1, 1, Tq, L]
@@ -1721,15 +1798,7 @@ def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspa
         raise C.OQError(f"decode_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
     nkv, cap = k_cache.shape[1], k_cache.shape[2]
     q = q.contiguous()
-    mptr, mdt, mbs, mld = None, 0, 0, 0
-    if mask is not None:
-        if mask.dim() != 4 or mask.shape[1] != 1 or tuple(mask.shape[2:]) != (Tq, L) or mask.shape[0] not in (1, bs):
-            raise C.OQError(f"decode_attention: mask {tuple(mask.shape)} (expected [{bs} | 1, 1, {Tq}, {L}])")
-        if mask.stride(3) != 1:
-            mask = mask.contiguous()
-        mptr, mdt = C.ptr(mask[:1, :1, :1, :1]), C.dt(mask)
-        mbs = mask.stride(0) if mask.shape[0] == bs and bs > 1 else 0
-        mld = mask.stride(2) if Tq > 1 else 0
+    mask, mptr, mdt, mbs, mld = _decode_mask("decode_attention", mask, bs, Tq, L)
     ws_n = C.size_call("oq_attn_decode_workspace", bs, nh, nkv, Tq, int(L), hd)
     if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)

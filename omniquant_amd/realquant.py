@@ -275,9 +275,20 @@ def _replace_module(root, name, new):
     setattr(root.get_submodule(parent), leaf, new)
 
 
-def _mark_packed(qlayer, act_bits, act_quant=False):
-    """The block's forward checks this once at entry and takes the packed inference path (block_common.packed_guard)."""
-    qlayer._oq_packed = {"act_bits": int(act_bits), "act_quant": bool(act_quant)}
+def _mark_packed(qlayer, act_bits, act_quant=False, kv_cache_bits=None):
+    """The block's forward checks this once at entry and takes the packed inference path (block_common.packed_guard).
+    kv_cache_bits (None or 4): the storage kind of the KV caches the block creates (kvcache.PackedKVCache code_bits)."""
+    qlayer._oq_packed = {"act_bits": int(act_bits), "act_quant": bool(act_quant), "kv_cache_bits": kv_cache_bits}
+
+
+def _check_kv_cache_bits(kv_cache_bits, act_quant):
+    if kv_cache_bits is None:
+        return
+    if kv_cache_bits != 4:
+        raise C.OQError(f"kv_cache_bits {kv_cache_bits} (None: float rows, or 4)")
+    if not act_quant:
+        raise C.OQError("kv_cache_bits=4 needs act_quant=True: a weight-only block's k / v are not on a 4-bit grid, and quantising "
+                        "them for the cache would change the model")
 
 
 def _check_a4_quantizer(name, q, bits):
@@ -336,12 +347,15 @@ def check_act_quant_eligible(qlayer, wbits, group_size=None):
                 _check_a4_quantizer(name + ".x2_quantizer", m.x2_quantizer, 4)
 
 
-def pack_block(qlayer, wbits, act_quant=False):
+def pack_block(qlayer, wbits, act_quant=False, kv_cache_bits=None):
     """Replace every folded QuantLinear of a calibrated block by a PackedLinear (quantize/omniquant.py:255-278) and mark the
     block packed: its forward then runs the weight-only inference path.  act_quant=True (W4A4 LLaMA blocks,
     check_act_quant_eligible): the same buffers -- the state_dict is the weight-only pack's -- with act_bits 4 linears, and
-    the forward runs the integer path (llama_block.QuantLlamaDecoderLayer._packed_forward_a4)."""
+    the forward runs the integer path (llama_block.QuantLlamaDecoderLayer._packed_forward_a4).  kv_cache_bits=4 (with
+    act_quant=True): the block's KV caches store the head quantisers' 4-bit codes (kvcache.PackedKVCache code_bits); the values
+    the attention reads are the same."""
     from .linear import QuantLinear
+    _check_kv_cache_bits(kv_cache_bits, act_quant)
     act_bits = _act_bits(qlayer)
     if act_quant:
         check_act_quant_eligible(qlayer, wbits)
@@ -352,17 +366,18 @@ def pack_block(qlayer, wbits, act_quant=False):
         packed = pack_linear(module.weight.float(), wq.scales, wq.zeros, wbits, wq.group_size, module.bias)
         _replace_module(qlayer, name, PackedLinear(wbits, wq.group_size, module.in_features, module.out_features, packed,
                                                    act_bits=4 if act_quant else 16))
-    _mark_packed(qlayer, act_bits, act_quant)
+    _mark_packed(qlayer, act_bits, act_quant, kv_cache_bits)
     return qlayer
 
 
-def load_packed_block(qlayer, state_dict, wbits, group_size, act_quant=False):
+def load_packed_block(qlayer, state_dict, wbits, group_size, act_quant=False, kv_cache_bits=None):
     """Turn a fresh Quant*DecoderLayer (built from the model's layer and the run's args, not calibrated) into the packed block
     whose state_dict() this is, without recalibrating: every QuantLinear becomes an empty PackedLinear, the LET-folded norm
     biases get their buffers, then the state dict is loaded (float LET / LWC learnables it still holds are not needed for
     inference and are ignored; any missing tensor is an error)."""
     from .linear import QuantLinear
     from .norm import OmniLayerNorm, OmniLlamaRMSNorm
+    _check_kv_cache_bits(kv_cache_bits, act_quant)
     act_bits = _act_bits(qlayer)
     if act_quant:
         check_act_quant_eligible(qlayer, wbits, group_size or 0)
@@ -378,5 +393,5 @@ def load_packed_block(qlayer, state_dict, wbits, group_size, act_quant=False):
     missing, _ = qlayer.load_state_dict(state_dict, strict=False)
     if missing:
         raise C.OQError(f"load_packed_block: the state dict lacks {missing}")
-    _mark_packed(qlayer, act_bits, act_quant)
+    _mark_packed(qlayer, act_bits, act_quant, kv_cache_bits)
     return qlayer

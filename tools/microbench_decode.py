@@ -10,7 +10,13 @@
    eager host time per forward call, and the HIP launches of the step (C-ABI calls counted on the host).
    `--step-only --steps N` runs N eager steps and nothing else (for a `rocprofv3 --kernel-trace --stats` run of its own).
 
-usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
+3. `--codes`: instead of 1 and 2, oq_attn_decode_codes on a 4-bit code cache (72 bytes per head row of 128) against
+   oq_attn_decode on the bf16 cache, same shape table, same process, both on cold cache sets (the code cache rotates through
+   more sets: each is smaller).  The two graphs are replayed alternately `--rounds` times; a row reports the median, minimum
+   and maximum of each kernel, the bf16 kernel's own run-to-run spread (max - min over its median) and the ratio of the
+   medians.
+
+usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N] [--codes [--rounds 7]]
 """
 import argparse
 import json
@@ -90,6 +96,70 @@ def kernel_rows(reps, quick, dev):
                 rows.append(r)
                 print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
                 del sets
+                torch.cuda.empty_cache()
+    return rows
+
+
+def codes_rows(reps, rounds, quick, dev):
+    rows = []
+    for name, nh, nkv, hd in SHAPES:
+        for bs in BS:
+            for L in LS:
+                if quick and (bs != 1 or L not in (2048, 8192)):
+                    continue
+                kv_bytes = 2 * bs * nkv * L * hd * 2
+                code_bytes = 2 * bs * nkv * L * (hd // 2 + 8)
+                q = torch.randn(bs, 1, nh, hd, device=dev).bfloat16()
+                o = torch.empty_like(q)
+                ws = torch.empty(C.size_call("oq_attn_decode_workspace", bs, nh, nkv, 1, L, hd), dtype=torch.uint8, device=dev)
+                scale = hd ** -0.5
+                fsets = [(torch.randn(bs, nkv, L, hd, device=dev).bfloat16(), torch.randn(bs, nkv, L, hd, device=dev).bfloat16())
+                         for _ in range(max(2, -(-COLD_BYTES // kv_bytes)))]
+
+                def meta():      # scales and integer zero-points of the size a 4-bit grid over N(0, 1) rows has
+                    m = torch.empty(bs, nkv, L, 2, device=dev)
+                    m[..., 0] = torch.rand(bs, nkv, L, device=dev) * 0.1 + 0.3
+                    m[..., 1] = torch.randint(5, 11, (bs, nkv, L), device=dev).float()
+                    return m
+
+                csets = [(torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev),
+                          torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev), meta(), meta())
+                         for _ in range(max(2, -(-COLD_BYTES // code_bytes)))]
+                graphs = []
+                for fns in ([(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)) for s in fsets],
+                            [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in csets]):
+                    for f in fns:
+                        f()
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        for _ in range(reps):
+                            for f in fns:
+                                f()
+                    g.replay()
+                    torch.cuda.synchronize()
+                    graphs.append((g, reps * len(fns)))
+                us = ([], [])
+                for _ in range(rounds):
+                    for i, (g, n) in enumerate(graphs):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        g.replay()
+                        b.record()
+                        torch.cuda.synchronize()
+                        us[i].append(a.elapsed_time(b) * 1000.0 / n)
+                med = [sorted(u)[len(u) // 2] for u in us]
+                r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, L=L, Tq=1, dtype="bfloat16", cache="cold", rounds=rounds,
+                         bf16_sets=len(fsets), code_sets=len(csets),
+                         bf16_us=med[0], bf16_us_min=min(us[0]), bf16_us_max=max(us[0]),
+                         bf16_spread=(max(us[0]) - min(us[0])) / med[0],
+                         codes_us=med[1], codes_us_min=min(us[1]), codes_us_max=max(us[1]),
+                         codes_spread=(max(us[1]) - min(us[1])) / med[1],
+                         codes_over_bf16=med[1] / med[0], bf16_GBps=kv_bytes / med[0] / 1e3, codes_GBps=code_bytes / med[1] / 1e3,
+                         codes_frac_hbm=code_bytes / med[1] * 1e6 / HBM_BPS)
+                rows.append(r)
+                print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+                del fsets, csets, graphs
                 torch.cuda.empty_cache()
     return rows
 
@@ -191,6 +261,8 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--step-only", action="store_true", help="only N eager decode steps of the 7B block (for rocprofv3)")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--codes", action="store_true", help="the code-cache kernel interleaved with the bf16-cache kernel")
+    ap.add_argument("--rounds", type=int, default=7, help="--codes: alternating replays of the two graphs")
     a = ap.parse_args()
     dev = "cuda:0"
     if not torch.cuda.is_available():
@@ -199,8 +271,11 @@ def main():
     if a.step_only:
         block_step(dev, a.reps, steps_only=a.steps)
         return
-    rows = kernel_rows(a.reps, a.quick, dev)
-    rows.append(block_step(dev, a.reps))
+    if a.codes:
+        rows = codes_rows(a.reps, a.rounds, a.quick, dev)
+    else:
+        rows = kernel_rows(a.reps, a.quick, dev)
+        rows.append(block_step(dev, a.reps))
     if a.out:
         with open(a.out, "w") as f:
             for r in rows:

@@ -9,7 +9,11 @@ Cache state as tools/microbench_packed.py: decode rows rotate through enough dis
 than the 256 MiB Infinity Cache (every launch streams its weight from HBM); prefill rows rotate through 2 sets.  Every
 number is the mean per launch of one captured graph of `reps` rounds, replayed once warm and once under hipEvents.
 
-usage: python tools/microbench_packed_a4.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
+`--step-only --kv-codes`: instead of N eager steps, the W4A4 block's decode step (bs 1, L 2048) on the bf16 cache and on a
+4-bit code cache (PackedKVCache(code_bits=4)), one captured graph each, replayed alternately `--rounds` times: median,
+minimum and maximum device time per step of both, and the ratio of the medians.
+
+usage: python tools/microbench_packed_a4.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N [--kv-codes --rounds 7]]
 """
 import argparse
 import json
@@ -208,6 +212,63 @@ def block_rows(dev, reps, steps_only=0):
     return rows
 
 
+def step_kv_codes(dev, reps, rounds):
+    """The W4A4 7B block's decode step on the bf16 cache and on the code cache, interleaved."""
+    from omniquant_amd.kvcache import PackedKVCache
+    L = 2048
+    blk, cfg = packed_7b_block(dev, True)
+    H, nh = cfg.hidden_size, cfg.num_attention_heads
+    x = (torch.randn(1, 1, H, device=dev) * 0.5).bfloat16()
+    pos = torch.tensor([[L - 1]], device=dev)
+    caches = [PackedKVCache(1, nh, H // nh, torch.bfloat16, dev, capacity=L + 64),
+              PackedKVCache(1, nh, H // nh, torch.bfloat16, dev, capacity=L + 64, code_bits=4)]
+    caches[0].k.normal_()
+    caches[0].v.normal_()
+    for codes, meta in ((caches[1].k_codes, caches[1].k_meta), (caches[1].v_codes, caches[1].v_meta)):
+        codes.copy_(torch.randint(0, 256, codes.shape, dtype=torch.uint8, device=dev))
+        meta[..., 0] = 0.35
+        meta[..., 1] = 8.0
+    graphs, calls = [], []
+    for cache in caches:
+        def step(cache=cache):
+            cache.length = L - 1
+            with torch.no_grad():
+                return blk(x, attention_mask=None, position_ids=pos, past_key_value=cache, use_cache=True)[0]
+        names = []
+        orig = C.call
+        C.call = lambda name, *a: names.append(name) or orig(name, *a)
+        try:
+            step()
+        finally:
+            C.call = orig
+        calls.append(sorted(set(names)))
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(reps * 10):
+                step()
+        g.replay()
+        torch.cuda.synchronize()
+        graphs.append(g)
+    us = ([], [])
+    for _ in range(rounds):
+        for i, g in enumerate(graphs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            us[i].append(a.elapsed_time(b) * 1000.0 / (reps * 10))
+    med = [sorted(u)[len(u) // 2] for u in us]
+    r = dict(what="packed llama-7b W4A4 per-channel block decode step, bf16 cache vs 4-bit code cache", bs=1, L=L,
+             dtype="bfloat16", rounds=rounds, bf16_cache_us=round(med[0], 2), bf16_cache_us_min=round(min(us[0]), 2),
+             bf16_cache_us_max=round(max(us[0]), 2), code_cache_us=round(med[1], 2), code_cache_us_min=round(min(us[1]), 2),
+             code_cache_us_max=round(max(us[1]), 2), code_over_bf16=round(med[1] / med[0], 4),
+             cache_bytes=[c.nbytes() for c in caches], code_cache_capi_calls=calls[1])
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -215,15 +276,22 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--step-only", action="store_true", help="only N eager W4A4 decode steps of the 7B block (for rocprofv3)")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--kv-codes", action="store_true", help="with --step-only: the step on the bf16 cache vs the 4-bit code cache")
+    ap.add_argument("--rounds", type=int, default=7, help="--kv-codes: alternating replays of the two graphs")
     a = ap.parse_args()
     dev = "cuda:0"
     if not torch.cuda.is_available():
         raise SystemExit("microbench_packed_a4 needs a GPU")
     C.load()
-    if a.step_only:
+    if a.kv_codes and not a.step_only:
+        ap.error("--kv-codes goes with --step-only")
+    if a.step_only and a.kv_codes:
+        rows = step_kv_codes(dev, a.reps, a.rounds)
+    elif a.step_only:
         block_rows(dev, a.reps, steps_only=a.steps)
         return
-    rows = kernel_rows(a.reps, a.quick, dev) + block_rows(dev, a.reps)
+    else:
+        rows = kernel_rows(a.reps, a.quick, dev) + block_rows(dev, a.reps)
     if a.out:
         with open(a.out, "w") as f:
             for r in rows:
