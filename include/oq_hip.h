@@ -380,6 +380,37 @@ int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes
                          int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, float scale,
                          const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
                          int64_t workspace_bytes, void* stream);
+/*   Ragged batches: one length per sequence, on the device.  lens int32 [bs] = the rows each sequence holds BEFORE this step;
+ *      no launch parameter depends on its values, so a step needs no host read, no padding mask and no position tensor.
+ *   oq_kv_append_ragged / oq_kv_append_quant_ragged / oq_kv_append_quant_codes_ragged: the three appends with lens in the place
+ *      of past: sequence b's step row t goes to cache row lens[b] + t and, with pos == NULL, rotates at position lens[b] + t
+ *      (clamped to the table).  Every other argument, and every value written, is that of the uniform entry point called on the
+ *      sequence alone with past = lens[b].  The kernel guards the range the host cannot see: a row with lens[b] + t outside
+ *      [0, cap) is not stored to the cache / codes / meta (skipped, not clamped); q_out / k_out / v_out are complete.
+ *   oq_attn_decode_ragged / oq_attn_decode_codes_ragged: the two attentions without a mask: query row t of sequence b attends
+ *      cache rows j <= lens[b] + t (causal within the step).  L_bound (Tq <= L_bound <= cap) is an upper bound of lens[b] + Tq
+ *      over the batch: the split plan and the workspace (oq_attn_decode_workspace with L = L_bound) depend on it and the shape
+ *      only.  Rows >= lens[b] + Tq are never read.  lens[b] < 0 counts as 0 and lens[b] > L_bound - Tq as L_bound - Tq, so every
+ *      query row has at least one key and no read leaves [0, L_bound).  With every lens[b] == L_bound - 1 and Tq == 1 the output
+ *      is oq_attn_decode's (L = L_bound, mask = NULL) bit for bit. */
+int oq_kv_append_ragged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
+                        int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens,
+                        const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream);
+int oq_kv_append_quant_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                              void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                              int64_t cap, const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                              int64_t pos_bstride, int nbits, void* stream);
+int oq_kv_append_quant_codes_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                    void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs,
+                                    int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens, const float* cos,
+                                    const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits, void* stream);
+int oq_attn_decode_ragged(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq,
+                          int nh, int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                                void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                                const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 /* ---- fused causal attention (models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using

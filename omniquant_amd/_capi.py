@@ -82,6 +82,15 @@ SIGNATURES = {
                                  _vp, _vp, _i64, _vp, _i64, _i32, _vp],
     "oq_attn_decode_codes": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _i32, _i64, _i64,
                              _vp, _i64, _vp],
+    "oq_kv_append_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp,
+                            _i64, _vp],
+    "oq_kv_append_quant_ragged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _vp,
+                                  _vp, _i64, _vp, _i64, _i32, _vp],
+    "oq_kv_append_quant_codes_ragged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32,
+                                        _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "oq_attn_decode_ragged": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
+    "oq_attn_decode_codes_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp,
+                                    _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,

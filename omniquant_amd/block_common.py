@@ -93,6 +93,30 @@ class QuantBlockMixin:
         raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
 
     @staticmethod
+    def _new_tokens_in(new_tokens, past_key_value, bsz, T, device):
+        """new_tokens (the valid step rows per sequence of a right-padded ragged step) as (int32 [bs] device tensor or None,
+        what the cache's host bound grows by).  None: all T rows.  A Python sequence of ints is checked (0 <= n <= T) and
+        uploaded, and the bound grows by its maximum; a device tensor is taken as it is -- its values are never read -- and
+        the bound grows by T.  Without a ragged PackedKVCache as past_key_value it is refused."""
+        from ._capi import OQError
+        if new_tokens is None:
+            return None, T
+        if not getattr(past_key_value, "ragged", False):
+            raise OQError("new_tokens needs a ragged PackedKVCache as past_key_value (PackedKVCache(..., ragged=True))")
+        if torch.is_tensor(new_tokens):
+            if new_tokens.dtype != torch.int32 or tuple(new_tokens.shape) != (bsz,) or new_tokens.device != device:
+                raise OQError(f"new_tokens: expected an int32 [{bsz}] tensor on {device}, got {tuple(new_tokens.shape)} "
+                              f"{new_tokens.dtype} on {new_tokens.device}")
+            return new_tokens, T
+        try:
+            seq = [new_tokens[i].__index__() for i in range(len(new_tokens))]
+        except (TypeError, AttributeError):
+            raise OQError(f"new_tokens: expected {bsz} ints or an int32 [{bsz}] device tensor, got {new_tokens!r}") from None
+        if len(seq) != bsz or min(seq) < 0 or max(seq) > T:
+            raise OQError(f"new_tokens {seq}: one count in [0, {T}] for each of the {bsz} sequences")
+        return torch.tensor(seq, dtype=torch.int32).to(device, non_blocking=True), max(seq)
+
+    @staticmethod
     def _positions(position_ids, past, bsz, T, device):
         """position_ids (None: past .. past + T - 1; [T]; [1 | bs, T]) as the int64 [1 | bs, T] tensor the append gathers at."""
         if position_ids is None:
@@ -102,18 +126,39 @@ class QuantBlockMixin:
             raise ValueError(f"position_ids of shape {tuple(position_ids.shape)} for a batch of {bsz} x {T} tokens")
         return pos.to(device=device, dtype=torch.int64)
 
-    def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None, head_bits=None):
+    def _step_positions(self, position_ids, cache, bsz, T, device):
+        """_positions at the cache's length; None for a ragged cache with a past and no position_ids: the append kernel then
+        rotates sequence b's row t at lengths[b] + t, and no position tensor is built."""
+        if cache.ragged and cache.length > 0 and position_ids is None:
+            return None
+        return self._positions(position_ids, cache.length, bsz, T, device)
+
+    def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None, head_bits=None,
+                          new_tokens=(None, None)):
         """Attention of this step's q [bs, Tq, nh, hd] over the cache plus this step's k / v, which are appended to it (rotated
         by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
         (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation.
         head_bits (W4A4 blocks): q / k / v (float32 or the cache's dtype) also pass the per-(token, head) quantiser of that
         width in the append's launch, so the cache holds, and the attention reads, the quantised values in the cache's dtype.
         A code cache (cache.code_bits 4) receives the codes instead (oq_kv_append_quant_codes) and steps with a past run
-        oq_attn_decode_codes on them; its prefill runs the same attention launches on the same q / k / v values."""
+        oq_attn_decode_codes on them; its prefill runs the same attention launches on the same q / k / v values.
+        A ragged cache (cache.ragged): the append and the attention read the same pre-step cache.lengths on the device
+        (lengths= of the ops), `past` and L are host bounds, and the step's rows are right-padded: new_tokens = (counts or None
+        for all Tq, growth of the bound) from _new_tokens_in says how many rows of each sequence count.  All Tq rows are
+        written; rows at or beyond a sequence's new length are scratch that its next step overwrites, and the outputs of pad
+        query rows are finite and unspecified.  With cache.length == 0 this is the prefill above (the caller's causal mask
+        keeps right padding away from the valid rows; the append goes at lengths = 0).  With a past the mask must be None
+        (row t of sequence b attends rows <= lengths[b] + t) and positions None leaves them to the kernel (lengths[b] + t).
+        A decode step on a ragged cache performs no device-to-host read and builds no mask or position tensor."""
         from . import ops
+        from ._capi import OQError
         bsz, Tq = q.shape[0], q.shape[1]
         past = cache.length
         L = past + Tq
+        lens = cache.lengths if cache.ragged else None
+        if lens is not None and past > 0 and attention_mask is not None:
+            raise OQError("a ragged cache with a past takes no attention_mask: each sequence attends its own rows "
+                          "(pass attention_mask=None)")
         if attention_mask is not None and (attention_mask.dim() != 4 or attention_mask.shape[0] not in (1, bsz)
                                            or tuple(attention_mask.shape[1:]) != (1, Tq, L)):
             raise ValueError(f"Attention mask should be of size {(bsz, 1, Tq, L)}, but is {attention_mask.size()}")
@@ -123,26 +168,35 @@ class QuantBlockMixin:
         if head_bits is None:
             qr = torch.empty_like(q) if rot else q
             kr, vr = torch.empty_like(k) if (rot and past == 0) else None, None
-            ops.kv_append(k, v, cache.k, cache.v, past, q=q if rot else None, q_out=qr if rot else None, k_out=kr, cos=cos, sin=sin,
-                          positions=positions)
+            ops.kv_append(k, v, cache.k, cache.v, 0 if cache.ragged else past, q=q if rot else None, q_out=qr if rot else None,
+                          k_out=kr, cos=cos, sin=sin, positions=positions, lengths=lens)
         else:
             qr = torch.empty(q.shape, dtype=cache.dtype, device=q.device)
             kr, vr = (torch.empty(k.shape, dtype=cache.dtype, device=q.device) for _ in range(2)) if past == 0 else (None, None)
             if cache.code_bits is not None:
-                ops.kv_append_codes(k, v, cache.dtype, cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta, past=past, q=q,
-                                    q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions)
+                ops.kv_append_codes(k, v, cache.dtype, cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta,
+                                    past=0 if cache.ragged else past, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin,
+                                    positions=positions, lengths=lens)
             else:
-                ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=past, q=q, q_out=qr,
-                                    k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions)
-        cache.length = L
+                ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=0 if cache.ragged else past,
+                                    q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions, lengths=lens)
+        if lens is None:
+            cache.length = L
         if past == 0:
             mask = attention_mask
             if mask is not None and mask.shape[0] != bsz:
                 mask = mask.expand(bsz, 1, Tq, L)
-            return self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
-        if cache.code_bits is not None:
-            return ops.decode_attention_codes(qr, cache, L, scale, attention_mask)
-        return ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask)
+            attn = self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
+        elif cache.code_bits is not None:
+            attn = ops.decode_attention_codes(qr, cache, L, scale, attention_mask, lengths=lens)
+        else:
+            attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask, lengths=lens)
+        if lens is not None:
+            # (after the attention, which reads the pre-step lengths; the stream orders the launches)
+            counts, grow = new_tokens
+            lens.add_(Tq if counts is None else counts)
+            cache.length = past + (Tq if grow is None else grow)
+        return attn
 
     @staticmethod
     def _packed_attention(q, k, v, attention_mask, scale):

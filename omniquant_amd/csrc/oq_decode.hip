@@ -39,12 +39,18 @@ struct AppendP {
     // 32-bit word d / 8, and one (scale, rounded zero-point) pair per row; value = (code - zp) * scale
     uint8_t *k_codes, *v_codes;
     float *k_meta, *v_meta;
+    // RAGGED instantiations: the rows before this step, per sequence, int32 [bs] on the device (`past` is not read)
+    const int32_t* lens;
 };
 
-template <typename TIN, typename T, bool QUANT, bool CODES>
+// RAGGED: sequence b's row t goes to cache row lens[b] + t (and rotates at that position when pos == NULL).  The host cannot
+// see lens, so the kernel guards the range itself: a row outside [0, cap) is not stored to the cache / codes / meta (skipped,
+// never clamped onto another row); its q_out / k_out / v_out rows are written like any other.
+template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED>
 __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     const int hd = p.hd, nh = p.nh, nkv = p.nkv;
-    const int64_t Tq = p.Tq, cap = p.cap, past = p.past;
+    const int64_t Tq = p.Tq, cap = p.cap;
+    int64_t past = p.past;
     const TIN* q = (const TIN*)p.q;
     const TIN* k = (const TIN*)p.k;
     const TIN* v = (const TIN*)p.v;
@@ -58,6 +64,11 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
         const int slot = (int)(r % nslot);
         r /= nslot;
         const int64_t t = r % Tq, b = r / Tq;
+        bool fits = true;
+        if constexpr (RAGGED) {
+            past = p.lens[b];
+            fits = past + t >= 0 && past + t < cap;
+        }
         const TIN* src;
         T* dst;
         T* dst2;
@@ -71,19 +82,19 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
         } else if (slot < nh + nkv) {
             const int h = slot - nh;
             src = k + ((b * Tq + t) * nkv + h) * hd;
-            dst = kc ? kc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst = kc && fits ? kc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
             dst2 = k_out ? k_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
             if constexpr (CODES) {
-                cdst = p.k_codes + ((b * nkv + h) * cap + past + t) * half;
+                cdst = fits ? p.k_codes + ((b * nkv + h) * cap + past + t) * half : nullptr;
                 mdst = p.k_meta + ((b * nkv + h) * cap + past + t) * 2;
             }
         } else {
             const int h = slot - nh - nkv;
             src = v + ((b * Tq + t) * nkv + h) * hd;
-            dst = vc ? vc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst = vc && fits ? vc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
             dst2 = v_out ? v_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
             if constexpr (CODES) {
-                cdst = p.v_codes + ((b * nkv + h) * cap + past + t) * half;
+                cdst = fits ? p.v_codes + ((b * nkv + h) * cap + past + t) * half : nullptr;
                 mdst = p.v_meta + ((b * nkv + h) * cap + past + t) * 2;
             }
             rot = false;
@@ -167,21 +178,25 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     }
 }
 
-template <typename TIN, typename T, bool QUANT, bool CODES>
+template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED>
 void launch_append(const AppendP& p, hipStream_t st) {
     const int64_t n = p.bs * p.Tq * (p.nh + 2 * p.nkv) * (p.hd / 16);
     const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT, CODES>), dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT, CODES, RAGGED>), dim3(grid), dim3(256), 0, st, p);
 }
 
 // The checks, the grid and the dtype dispatch both ABI entry points share (fn: the entry point's name for the messages).
 // The caller has checked what is its own: which pointers it requires, head_dim, nbits and the dtype pairs it admits.
-template <bool QUANT, bool CODES = false>
+template <bool QUANT, bool CODES = false, bool RAGGED = false>
 int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* stream) {
     OQ_CHECK_ARG(!p.q || p.q_out, "%s: q without q_out", fn);
     OQ_CHECK_ARG(p.bs > 0 && p.Tq > 0 && p.nkv > 0 && p.nh >= 0 && (p.q || p.nh == 0), "%s: bad shape", fn);
-    OQ_CHECK_ARG(!(p.kc || p.k_codes) || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
-                 (long long)p.past, (long long)(p.past + p.Tq), (long long)p.cap);
+    if constexpr (RAGGED) {
+        OQ_CHECK_ARG(p.lens && (uintptr_t)p.lens % 4 == 0 && p.cap >= 0, "%s: lens (int32 [bs] on the device), cap >= 0", fn);
+    } else {
+        OQ_CHECK_ARG(!(p.kc || p.k_codes) || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
+                     (long long)p.past, (long long)(p.past + p.Tq), (long long)p.cap);
+    }
     OQ_CHECK_ARG(!p.cs == !p.sn, "%s: cos and sin go together", fn);
     OQ_CHECK_ARG(!p.cs || (p.P > 0 && oq_aligned16(p.cs) && oq_aligned16(p.sn)), "%s: cos/sin tables must be 16-byte aligned, P > 0", fn);
     OQ_CHECK_ARG(p.pos_bs >= 0, "%s: pos_bstride", fn);
@@ -189,11 +204,11 @@ int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* s
     for (const void* ptr : ptrs) OQ_CHECK_ARG(!ptr || oq_aligned16(ptr), "%s: tensors must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == OQ_F32 && in_dtype == OQ_F32) {
-        launch_append<float, float, QUANT, CODES>(p, st);
+        launch_append<float, float, QUANT, CODES, RAGGED>(p, st);
     } else if (dtype == OQ_BF16 && in_dtype == OQ_BF16) {
-        launch_append<bf16_t, bf16_t, QUANT, CODES>(p, st);
+        launch_append<bf16_t, bf16_t, QUANT, CODES, RAGGED>(p, st);
     } else if constexpr (QUANT) {
-        launch_append<float, bf16_t, true, CODES>(p, st);       // f32 -> bf16: the only other pair the quantising entry admits
+        launch_append<float, bf16_t, true, CODES, RAGGED>(p, st);      // f32 -> bf16: the only other pair the quantising entry admits
     } else {
         oq_set_error("%s: dtype %d unsupported", fn, dtype);
         return OQ_E_UNSUPPORTED;
@@ -297,10 +312,17 @@ struct CodeKV {
 // Split kernel: grid (ns, nkv, bs).  Lane group `grp` (HD / DPL lanes) handles rows j0 + grp, j0 + grp + G, ... of the split,
 // U rows in flight; query rows are processed QB at a time (rows r = t*rep + i of this kv head).  Workspace per
 // (b, kv head, split, r): [m, l, acc[HD]] with m in the log2 domain.
-template <typename T, int HD, int QB, typename KV>
+// RAGGED: every sequence has its own length.  lens[b] rows precede this step (negative: 0; clamped to L - Tq, so that a length
+// beyond the bound the host planned with can neither read past row L nor leave a query without a key), L is the host's upper
+// bound of lens[b] + Tq (the split plan depends on it alone) and query row t sees rows j <= lens[b] + t: causal within the
+// step, no mask tensor.  Rows >= lens[b] + Tq are never loaded; a split that starts there writes (m, l) = (-inf, 0) partials,
+// which the combine kernel weighs with 0.  lens[b] is the same for the whole workgroup, so the trip counts stay uniform.  With
+// every lens[b] == L - Tq and Tq == 1 the loops and the order of every sum are those of the plain instantiation.
+template <typename T, int HD, int QB, typename KV, bool RAGGED>
 __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, const KV kv_all, float* ws, int64_t Tq, int nh,
                                                                   int nkv, int64_t cap, int64_t L, float scale, const void* mask,
-                                                                  int mdt, int64_t m_bs, int64_t m_ld, int ns) {
+                                                                  int mdt, int64_t m_bs, int64_t m_ld, int ns,
+                                                                  const int32_t* lens) {
     constexpr int DPL = KV::DPL;
     constexpr int LPK = HD / DPL;
     constexpr int GPW = 64 / LPK;
@@ -317,7 +339,14 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
     const int rep = nh / nkv;
     const int64_t R = (int64_t)rep * Tq;
     const int64_t chunk = (L + ns - 1) / ns;
-    const int64_t j0 = split * chunk, j1 = (j0 + chunk < L) ? j0 + chunk : L;
+    const int64_t j0 = split * chunk;
+    int64_t j1 = (j0 + chunk < L) ? j0 + chunk : L;
+    int64_t len = 0;
+    if constexpr (RAGGED) {
+        len = lens[b];
+        len = len < 0 ? 0 : (len > L - Tq ? L - Tq : len);
+        if (j1 > len + Tq) j1 = len + Tq;
+    }
     const KV kv = kv_all.at((b * nkv + kvh) * cap, d0);
     float* wsb = ws + ((b * nkv + kvh) * ns + split) * R * (HD + 2);
     const float zs = scale * log2e;
@@ -325,6 +354,7 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
     for (int64_t r0 = 0; r0 < R; r0 += QB) {
         float qv[QB][DPL], m[QB], l[QB], acc[QB][DPL];
         int64_t moff[QB];
+        int64_t vis[QB];                                            // RAGGED: the last cache row the query row sees
 #pragma unroll
         for (int rr = 0; rr < QB; ++rr) {
             const int64_t r = r0 + rr < R ? r0 + rr : R - 1;        // padding rows repeat the last one (never stored)
@@ -338,6 +368,7 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
                 for (int i = 0; i < 8; ++i) qv[rr][8 * n + i] = t8[i];
             }
             moff[rr] = b * m_bs + t * m_ld;
+            vis[rr] = len + t;
             m[rr] = -INFINITY;
             l[rr] = 0.f;
 #pragma unroll
@@ -371,13 +402,13 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
                     s = wave_sum(s, LPK);                       // every lane of the group holds q . k_j
                     if constexpr (KV::SCALED) s *= ok[u] ? kr[u].scale() : 0.f;
                     float zz;
-                    if (mask) {
+                    if (!RAGGED && mask) {
                         const float mv = ok[u] ? ld_mask(mask, mdt, moff[rr] + j) : 0.f;
                         zz = fmaxf((s * scale + mv) * log2e, lowest);   // max(z, -FLT_MAX) as oq_softmax_fwd, in log2 units
                     } else {
                         zz = s * zs;
                     }
-                    z[u][rr] = ok[u] ? zz : -INFINITY;
+                    z[u][rr] = (RAGGED ? ok[u] && j <= vis[rr] : ok[u]) ? zz : -INFINITY;
                 }
             }
 #pragma unroll
@@ -392,7 +423,10 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
 #pragma unroll
                 for (int i = 0; i < DPL; ++i) acc[rr][i] *= c;
 #pragma unroll
-                for (int u = 0; u < U; ++u) z[u][rr] = ok[u] ? __builtin_amdgcn_exp2f(z[u][rr] - mx) : 0.f;
+                for (int u = 0; u < U; ++u) {
+                    const bool sees = RAGGED ? ok[u] && jb + u * G + grp <= vis[rr] : ok[u];
+                    z[u][rr] = sees ? __builtin_amdgcn_exp2f(z[u][rr] - mx) : 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -478,12 +512,18 @@ struct DecP {
     int mdt;
     int64_t m_bs, m_ld;
     int ns;
+    const int32_t* lens;                // per-sequence lengths (the RAGGED instantiations), or NULL
 };
 
 template <typename T, int HD, int QB, typename KV>
 void launch_decode(const DecP& p, const KV& kv, hipStream_t st) {
-    hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV>), dim3(p.ns, p.nkv, p.bs), dim3(DEC_THREADS), 0, st, (const T*)p.q, kv,
-                       p.ws, p.Tq, p.nh, p.nkv, p.cap, p.L, p.scale, p.mask, p.mdt, p.m_bs, p.m_ld, p.ns);
+    const dim3 grid(p.ns, p.nkv, p.bs);
+    if (p.lens)
+        hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV, true>), grid, dim3(DEC_THREADS), 0, st, (const T*)p.q, kv, p.ws, p.Tq,
+                           p.nh, p.nkv, p.cap, p.L, p.scale, nullptr, 0, 0, 0, p.ns, p.lens);
+    else
+        hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV, false>), grid, dim3(DEC_THREADS), 0, st, (const T*)p.q, kv, p.ws, p.Tq,
+                           p.nh, p.nkv, p.cap, p.L, p.scale, p.mask, p.mdt, p.m_bs, p.m_ld, p.ns, nullptr);
     const int64_t rows = p.bs * (int64_t)p.nh * p.Tq;
     hipLaunchKernelGGL((attn_decode_combine_kernel<T, HD>), dim3(rows), dim3(HD), 0, st, (const float*)p.ws, (T*)p.o, p.Tq, p.nh,
                        p.nkv, p.ns);
@@ -513,16 +553,110 @@ void launch_decode_codes(int qb, const DecP& p, const void* kc, const void* vc, 
     }
 }
 
+// ---- what an entry point and its ragged form share: the entry's own checks, then kv_append<> / the decode launch.  lens ==
+//      NULL: the uniform form (`past`, resp. L and the mask); else the ragged one (fn carries the entry point's name). ------------
+int append_plain(const char* fn, const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
+                 int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past, const int32_t* lens,
+                 const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream) {
+    OQ_CHECK_ARG(k && v && k_cache && v_cache, "%s: null pointer", fn);
+    OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "%s: head_dim %d must be a multiple of 16", fn, hd);
+    const AppendP p{q, k, v, q_out, k_out, nullptr, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
+                    0, 0.f, nullptr, nullptr, nullptr, nullptr, lens};
+    return lens ? kv_append<false, false, true>(fn, p, dtype, dtype, stream) : kv_append<false>(fn, p, dtype, dtype, stream);
+}
+
+int append_quant(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                 void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
+                 const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                 int nbits, void* stream) {
+    OQ_CHECK_ARG(k && v, "%s: null k / v", fn);
+    OQ_CHECK_ARG(!k_cache == !v_cache, "%s: the k and v caches go together", fn);
+    OQ_CHECK_ARG(k_cache || (k_out && v_out), "%s: no destination for k / v (caches or k_out / v_out)", fn);
+    // (the DPP reduction over the hd / 16 lanes of a head needs a power-of-two lane group inside one row of 16)
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
+    OQ_CHECK_ARG(nbits >= 2 && nbits <= 8, "%s: %d-bit head quantiser (2..8)", fn, nbits);
+    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "%s: dtype %d (f32 or bf16)", fn, dtype);
+    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
+    const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
+                    nbits, 1.0f / (float)((1 << nbits) - 1), nullptr, nullptr, nullptr, nullptr, lens};
+    return lens ? kv_append<true, false, true>(fn, p, in_dtype, dtype, stream) : kv_append<true>(fn, p, in_dtype, dtype, stream);
+}
+
+int append_codes(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                 void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq, int nh, int nkv,
+                 int hd, int64_t cap, int64_t past, const int32_t* lens, const float* cos, const float* sin, int64_t P,
+                 const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
+    OQ_CHECK_ARG(k && v && k_codes && v_codes && k_meta && v_meta, "%s: null pointer", fn);
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
+    OQ_CHECK_ARG(nbits == 4, "%s: %d-bit codes (4)", fn, nbits);
+    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "%s: dtype %d (f32 or bf16)", fn, dtype);
+    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
+    OQ_CHECK_ARG(!k_out == !v_out, "%s: k_out and v_out go together", fn);
+    const AppendP p{q, k, v, q_out, k_out, v_out, nullptr, nullptr, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
+                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta, lens};
+    return lens ? kv_append<true, true, true>(fn, p, in_dtype, dtype, stream) : kv_append<true, true>(fn, p, in_dtype, dtype, stream);
+}
+
+// codes: k / v are the code buffers of a 4-bit cache and k_meta / v_meta its (scale, zero-point) pairs; else a float cache's
+// buffers (no meta).  ragged: lens is required and there is no mask; L is then the bound.
+int decode(const char* fn, bool codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
+           int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, const int32_t* lens, bool ragged,
+           float scale, const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
+           int64_t workspace_bytes, void* stream) {
+    OQ_CHECK_ARG(q && k && v && o && workspace && (!codes || (k_meta && v_meta)) && (!ragged || lens), "%s: null pointer", fn);
+    OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
+    OQ_CHECK_ARG(bs > 0 && bs <= 65535 && nkv > 0 && nkv <= 65535 && nh > 0 && nh % nkv == 0, "%s: bad heads %d / %d or batch %lld", fn,
+                 nh, nkv, (long long)bs);
+    OQ_CHECK_ARG(Tq > 0 && L >= Tq && L <= cap, "%s: need 1 <= Tq (%lld) <= L (%lld) <= cap (%lld)", fn, (long long)Tq, (long long)L,
+                 (long long)cap);
+    OQ_CHECK_ARG(!mask || mask_dtype == OQ_F32 || mask_dtype == OQ_F16 || mask_dtype == OQ_BF16, "%s: mask dtype %d", fn, mask_dtype);
+    OQ_CHECK_ARG(mask_bstride >= 0 && mask_ld >= 0, "%s: negative mask strides", fn);
+    OQ_CHECK_ARG(oq_aligned16(q) && oq_aligned16(k) && oq_aligned16(v) && oq_aligned16(o) && oq_aligned16(workspace) &&
+                     oq_aligned16(k_meta) && oq_aligned16(v_meta) && (uintptr_t)lens % 4 == 0,
+                 "%s: q, o, the cache buffers and the workspace must be 16-byte aligned (lens: 4)", fn);
+    const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
+    OQ_CHECK_ARG(workspace_bytes >= need, "%s: workspace %lld < %lld bytes", fn, (long long)workspace_bytes, (long long)need);
+    const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
+    const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L),
+                 lens};
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype != OQ_F32 && dtype != OQ_BF16) {
+        oq_set_error("%s: dtype %d unsupported", fn, dtype);
+        return OQ_E_UNSUPPORTED;
+    }
+    const bool f32 = dtype == OQ_F32;
+    if (codes) {
+        if (f32 && hd == 64) launch_decode_codes<float, 64>(qb, p, k, v, k_meta, v_meta, st);
+        else if (f32) launch_decode_codes<float, 128>(qb, p, k, v, k_meta, v_meta, st);
+        else if (hd == 64) launch_decode_codes<bf16_t, 64>(qb, p, k, v, k_meta, v_meta, st);
+        else launch_decode_codes<bf16_t, 128>(qb, p, k, v, k_meta, v_meta, st);
+    } else {
+        if (f32 && hd == 64) launch_decode_float<float, 64>(qb, p, k, v, st);
+        else if (f32) launch_decode_float<float, 128>(qb, p, k, v, st);
+        else if (hd == 64) launch_decode_float<bf16_t, 64>(qb, p, k, v, st);
+        else launch_decode_float<bf16_t, 128>(qb, p, k, v, st);
+    }
+    OQ_CHECK_LAUNCH(fn);
+    return OQ_OK;
+}
+
 }  // namespace
 
 extern "C" int oq_kv_append(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
                             int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
                             const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                             void* stream) {
-    OQ_CHECK_ARG(k && v && k_cache && v_cache, "oq_kv_append: null pointer");
-    OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "oq_kv_append: head_dim %d must be a multiple of 16", hd);
-    const AppendP p{q, k, v, q_out, k_out, nullptr, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride, 0, 0.f};
-    return kv_append<false>("oq_kv_append", p, dtype, dtype, stream);
+    return append_plain("oq_kv_append", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, past, nullptr, cos,
+                        sin, P, pos, pos_bstride, stream);
+}
+
+extern "C" int oq_kv_append_ragged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache,
+                                   void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                                   const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                                   int64_t pos_bstride, void* stream) {
+    OQ_CHECK_ARG(lens, "oq_kv_append_ragged: null lens");
+    return append_plain("oq_kv_append_ragged", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, 0, lens, cos,
+                        sin, P, pos, pos_bstride, stream);
 }
 
 extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd) {
@@ -533,51 +667,32 @@ extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t
 extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq,
                               int nh, int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype,
                               int64_t mask_bstride, int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
-    OQ_CHECK_ARG(q && k_cache && v_cache && o && workspace, "oq_attn_decode: null pointer");
-    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_attn_decode: head_dim %d (64 or 128)", hd);
-    OQ_CHECK_ARG(bs > 0 && bs <= 65535 && nkv > 0 && nkv <= 65535 && nh > 0 && nh % nkv == 0,
-                 "oq_attn_decode: bad heads %d / %d or batch %lld", nh, nkv, (long long)bs);
-    OQ_CHECK_ARG(Tq > 0 && L >= Tq && L <= cap, "oq_attn_decode: need 1 <= Tq (%lld) <= L (%lld) <= cap (%lld)", (long long)Tq,
-                 (long long)L, (long long)cap);
-    OQ_CHECK_ARG(!mask || mask_dtype == OQ_F32 || mask_dtype == OQ_F16 || mask_dtype == OQ_BF16, "oq_attn_decode: mask dtype %d",
-                 mask_dtype);
-    OQ_CHECK_ARG(mask_bstride >= 0 && mask_ld >= 0, "oq_attn_decode: negative mask strides");
-    OQ_CHECK_ARG(oq_aligned16(q) && oq_aligned16(k_cache) && oq_aligned16(v_cache) && oq_aligned16(o) && oq_aligned16(workspace),
-                 "oq_attn_decode: q, o, caches and workspace must be 16-byte aligned");
-    const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
-    OQ_CHECK_ARG(workspace_bytes >= need, "oq_attn_decode: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-    const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
-    const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L)};
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == OQ_F32) {
-        if (hd == 64) launch_decode_float<float, 64>(qb, p, k_cache, v_cache, st);
-        else launch_decode_float<float, 128>(qb, p, k_cache, v_cache, st);
-    } else if (dtype == OQ_BF16) {
-        if (hd == 64) launch_decode_float<bf16_t, 64>(qb, p, k_cache, v_cache, st);
-        else launch_decode_float<bf16_t, 128>(qb, p, k_cache, v_cache, st);
-    } else {
-        oq_set_error("oq_attn_decode: dtype %d unsupported", dtype);
-        return OQ_E_UNSUPPORTED;
-    }
-    OQ_CHECK_LAUNCH("oq_attn_decode");
-    return OQ_OK;
+    return decode("oq_attn_decode", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
+                  scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_decode_ragged(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs,
+                                     int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound,
+                                     float scale, void* workspace, int64_t workspace_bytes, void* stream) {
+    return decode("oq_attn_decode_ragged", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+                  true, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
                                   void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
                                   int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P, const int64_t* pos,
                                   int64_t pos_bstride, int nbits, void* stream) {
-    OQ_CHECK_ARG(k && v, "oq_kv_append_quant: null k / v");
-    OQ_CHECK_ARG(!k_cache == !v_cache, "oq_kv_append_quant: the k and v caches go together");
-    OQ_CHECK_ARG(k_cache || (k_out && v_out), "oq_kv_append_quant: no destination for k / v (caches or k_out / v_out)");
-    // (the DPP reduction over the hd / 16 lanes of a head needs a power-of-two lane group inside one row of 16)
-    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_kv_append_quant: head_dim %d (64 or 128)", hd);
-    OQ_CHECK_ARG(nbits >= 2 && nbits <= 8, "oq_kv_append_quant: %d-bit head quantiser (2..8)", nbits);
-    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "oq_kv_append_quant: dtype %d (f32 or bf16)", dtype);
-    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "oq_kv_append_quant: input dtype %d (f32 or the output dtype)", in_dtype);
-    const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    nbits, 1.0f / (float)((1 << nbits) - 1)};
-    return kv_append<true>("oq_kv_append_quant", p, in_dtype, dtype, stream);
+    return append_quant("oq_kv_append_quant", q, k, v, in_dtype, q_out, k_out, v_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap,
+                        past, nullptr, cos, sin, P, pos, pos_bstride, nbits, stream);
+}
+
+extern "C" int oq_kv_append_quant_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                         void* v_out, void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh,
+                                         int nkv, int hd, int64_t cap, const int32_t* lens, const float* cos, const float* sin,
+                                         int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
+    OQ_CHECK_ARG(lens, "oq_kv_append_quant_ragged: null lens");
+    return append_quant("oq_kv_append_quant_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd,
+                        cap, 0, lens, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
@@ -585,50 +700,32 @@ extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void
                                         int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
                                         const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                                         int nbits, void* stream) {
-    OQ_CHECK_ARG(k && v && k_codes && v_codes && k_meta && v_meta, "oq_kv_append_quant_codes: null pointer");
-    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_kv_append_quant_codes: head_dim %d (64 or 128)", hd);
-    OQ_CHECK_ARG(nbits == 4, "oq_kv_append_quant_codes: %d-bit codes (4)", nbits);
-    OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "oq_kv_append_quant_codes: dtype %d (f32 or bf16)", dtype);
-    OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "oq_kv_append_quant_codes: input dtype %d (f32 or the output dtype)",
-                 in_dtype);
-    OQ_CHECK_ARG(!k_out == !v_out, "oq_kv_append_quant_codes: k_out and v_out go together");
-    const AppendP p{q, k, v, q_out, k_out, v_out, nullptr, nullptr, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta};
-    return kv_append<true, true>("oq_kv_append_quant_codes", p, in_dtype, dtype, stream);
+    return append_codes("oq_kv_append_quant_codes", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs,
+                        Tq, nh, nkv, hd, cap, past, nullptr, cos, sin, P, pos, pos_bstride, nbits, stream);
+}
+
+extern "C" int oq_kv_append_quant_codes_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                               void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype,
+                                               int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens,
+                                               const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                                               int64_t pos_bstride, int nbits, void* stream) {
+    OQ_CHECK_ARG(lens, "oq_kv_append_quant_codes_ragged: null lens");
+    return append_codes("oq_kv_append_quant_codes_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype,
+                        bs, Tq, nh, nkv, hd, cap, 0, lens, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
                                     const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
                                     int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
                                     int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
-    OQ_CHECK_ARG(q && k_codes && v_codes && k_meta && v_meta && o && workspace, "oq_attn_decode_codes: null pointer");
-    OQ_CHECK_ARG(hd == 64 || hd == 128, "oq_attn_decode_codes: head_dim %d (64 or 128)", hd);
-    OQ_CHECK_ARG(bs > 0 && bs <= 65535 && nkv > 0 && nkv <= 65535 && nh > 0 && nh % nkv == 0,
-                 "oq_attn_decode_codes: bad heads %d / %d or batch %lld", nh, nkv, (long long)bs);
-    OQ_CHECK_ARG(Tq > 0 && L >= Tq && L <= cap, "oq_attn_decode_codes: need 1 <= Tq (%lld) <= L (%lld) <= cap (%lld)",
-                 (long long)Tq, (long long)L, (long long)cap);
-    OQ_CHECK_ARG(!mask || mask_dtype == OQ_F32 || mask_dtype == OQ_F16 || mask_dtype == OQ_BF16,
-                 "oq_attn_decode_codes: mask dtype %d", mask_dtype);
-    OQ_CHECK_ARG(mask_bstride >= 0 && mask_ld >= 0, "oq_attn_decode_codes: negative mask strides");
-    OQ_CHECK_ARG(oq_aligned16(q) && oq_aligned16(k_codes) && oq_aligned16(v_codes) && oq_aligned16(k_meta) && oq_aligned16(v_meta) &&
-                     oq_aligned16(o) && oq_aligned16(workspace),
-                 "oq_attn_decode_codes: q, o, codes, meta and workspace must be 16-byte aligned");
-    const int64_t need = oq_attn_decode_workspace(bs, nh, nkv, Tq, L, hd);
-    OQ_CHECK_ARG(workspace_bytes >= need, "oq_attn_decode_codes: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                 (long long)need);
-    const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
-    const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L)};
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == OQ_F32) {
-        if (hd == 64) launch_decode_codes<float, 64>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
-        else launch_decode_codes<float, 128>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
-    } else if (dtype == OQ_BF16) {
-        if (hd == 64) launch_decode_codes<bf16_t, 64>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
-        else launch_decode_codes<bf16_t, 128>(qb, p, k_codes, v_codes, k_meta, v_meta, st);
-    } else {
-        oq_set_error("oq_attn_decode_codes: dtype %d unsupported", dtype);
-        return OQ_E_UNSUPPORTED;
-    }
-    OQ_CHECK_LAUNCH("oq_attn_decode_codes");
-    return OQ_OK;
+    return decode("oq_attn_decode_codes", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
+                  scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                           const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                           int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    return decode("oq_attn_decode_codes_ragged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+                  lens, true, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }

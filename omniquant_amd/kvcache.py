@@ -13,6 +13,13 @@ quantiser's codes instead of its fake-quant values: k_codes / v_codes uint8 [bs,
 per row.  A stored element's value is fp32((float(code) - zp) * scale) -- bit for bit what the float32 cache of the same block
 holds -- and dequantize() / unpack_codes() are that contract in plain torch.  72 bytes per head row of 128 instead of 256
 (bfloat16) or 512 (float32).
+
+ragged=True (either kind): every sequence of the batch has its own length.  `lengths` is an int32 [bs] tensor ON THE DEVICE,
+which the append and the attention kernels read themselves (ops.kv_append(..., lengths=), ops.decode_attention(..., lengths=)):
+sequence b's valid rows are [0, lengths[b]), a step needs no padding mask and no position tensor, and nothing about its
+launches depends on a length the host would have to read back.  `length` stays a host int, now an UPPER BOUND of
+lengths.max(): it sizes the buffers and the attention's split plan.  Rows of a sequence at or beyond its own length are
+scratch.  There is no common length, so the (k, v) tuple surface is refused; sequence(b) gives one sequence's rows.
 """
 import operator
 
@@ -32,7 +39,7 @@ def unpack_codes(codes, meta):
 
 
 class PackedKVCache:
-    def __init__(self, bs, nkv, hd, dtype, device, capacity=0, code_bits=None):
+    def __init__(self, bs, nkv, hd, dtype, device, capacity=0, code_bits=None, ragged=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise OQError(f"PackedKVCache needs a GPU device (got {device}); there is no CPU fallback")
@@ -49,6 +56,8 @@ class PackedKVCache:
             raise OQError(f"PackedKVCache: a code cache covers head_dim 64 and 128, not {self.hd}")
         self.code_bits = code_bits
         self.length = 0
+        self.ragged = bool(ragged)
+        self.lengths = torch.zeros(self.bs, dtype=torch.int32, device=device) if self.ragged else None
         self._allocate(int(capacity))
 
     def _buffers(self):
@@ -77,9 +86,56 @@ class PackedKVCache:
         """Bytes of device memory the cache's buffers hold (the whole capacity)."""
         return sum(getattr(self, n).numel() * getattr(self, n).element_size() for n in self._buffers())
 
+    def _no_tuple(self, what):
+        if self.ragged:
+            raise OQError(f"{what}: a ragged cache has no common length, hence no [bs, nkv, length, hd] tensors; "
+                          "sequence(b) gives one sequence's rows")
+
+    def set_lengths(self, lengths, bound=None):
+        """Set the per-sequence lengths of a ragged cache: rows at or beyond a sequence's length become scratch, so
+        set_lengths([n0, 0, n2]) hands slot 1 to a new prompt while the others keep theirs.  A Python sequence of ints gives
+        length = max(lengths) (or `bound`, if larger) with no device read; an int32 [bs] device tensor is copied as it is and
+        needs the explicit host `bound` >= its maximum that `length` becomes."""
+        if not self.ragged:
+            raise OQError("set_lengths: not a ragged cache (PackedKVCache(..., ragged=True))")
+        if torch.is_tensor(lengths):
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (self.bs,) or lengths.device != self.device:
+                raise OQError(f"set_lengths: expected an int32 [{self.bs}] tensor on {self.device}, got {tuple(lengths.shape)} "
+                              f"{lengths.dtype} on {lengths.device}")
+            if bound is None:
+                raise OQError("set_lengths: a device tensor needs bound= (the host never reads the lengths back)")
+            top = int(bound)
+        else:
+            seq = [operator.index(n) for n in lengths]
+            if len(seq) != self.bs or min(seq) < 0:
+                raise OQError(f"set_lengths: {seq} for a batch of {self.bs} (one length >= 0 per sequence)")
+            top = max(seq) if bound is None else int(bound)
+            if top < max(seq):
+                raise OQError(f"set_lengths: bound {top} below the longest sequence ({max(seq)})")
+            lengths = torch.tensor(seq, dtype=torch.int32)
+        if not 0 <= top <= self.capacity:
+            raise OQError(f"set_lengths: bound {top} outside the capacity {self.capacity}")
+        self.lengths.copy_(lengths)
+        self.length = top
+
+    def sequence(self, b):
+        """(k, v) of sequence b of a ragged cache as [nkv, lengths[b], hd] copies in `dtype` (a code cache's are dequantised by
+        unpack_codes).  The one call that reads a length back from the device: for tests and debugging, not for the step."""
+        if not self.ragged:
+            raise OQError("sequence: not a ragged cache (index a uniform cache as (k, v))")
+        b = operator.index(b)
+        if not 0 <= b < self.bs:
+            raise IndexError(f"sequence {b} of a batch of {self.bs}")
+        n = min(max(int(self.lengths[b]), 0), self.capacity)
+        if self.code_bits is None:
+            return self.k[b, :, :n].clone(), self.v[b, :, :n].clone()
+        return tuple(unpack_codes(c[b, :, :n], m[b, :, :n]).to(self.dtype)
+                     for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
+
     def dequantize(self):
         """(k, v) as [bs, nkv, length, hd] tensors in `dtype`.  On a code cache these are fresh copies computed by
         unpack_codes (the value contract; one rounding to bfloat16 when that is the dtype); on a float cache, the views."""
+        self._no_tuple("dequantize")
         if self.code_bits is None:
             return self.k[:, :, :self.length], self.v[:, :, :self.length]
         n = self.length
@@ -101,6 +157,7 @@ class PackedKVCache:
     def __getitem__(self, i):
         """0 = keys, 1 = values, [bs, nkv, length, hd]: views of a float cache; of a code cache, dequantised COPIES, not views
         (writing to them does not change the cache)."""
+        self._no_tuple("indexing")
         if isinstance(i, slice):
             return (self[0], self[1])[i]
         i = operator.index(i)
@@ -113,18 +170,23 @@ class PackedKVCache:
         return (self.k if i == 0 else self.v)[:, :, :self.length]
 
     def __iter__(self):
+        self._no_tuple("iteration")
         yield from self.dequantize()
 
     def __repr__(self):
         return (f"PackedKVCache(bs={self.bs}, nkv={self.nkv}, hd={self.hd}, dtype={self.dtype}, length={self.length}, "
-                f"capacity={self.capacity}" + ("" if self.code_bits is None else f", code_bits={self.code_bits}") + ")")
+                f"capacity={self.capacity}" + ("" if self.code_bits is None else f", code_bits={self.code_bits}")
+                + (", ragged (length bounds the per-sequence lengths)" if self.ragged else "") + ")")
 
     @classmethod
-    def from_tuple(cls, kv, dtype=None, capacity=None, head_bits=None, code_bits=None):
+    def from_tuple(cls, kv, dtype=None, capacity=None, head_bits=None, code_bits=None, ragged=False):
         """A cache holding copies of the reference-layout (k, v), each [bs, nkv, T, hd] (any float dtype, converted once);
         the tensors passed in are never modified.  head_bits (W4A4 blocks): the rows are quantised per (token, head) over hd on
         that grid as they are imported (ops.kv_append_quant without rotation), which is what the block's own appends store.
-        code_bits=4 (with head_bits=4): the same quantisation, once, into a code cache."""
+        code_bits=4 (with head_bits=4): the same quantisation, once, into a code cache.
+        ragged: refused -- a tuple has one length for the whole batch."""
+        if ragged:
+            raise OQError("past_key_value: a (k, v) tuple has one length for the batch and cannot fill a ragged cache")
         if len(kv) != 2:
             raise OQError(f"past_key_value: expected (k, v), got {len(kv)} tensors")
         k, v = kv
@@ -152,10 +214,13 @@ class PackedKVCache:
 
     def to_tuple(self):
         """(k, v) as contiguous [bs, nkv, length, hd] copies (the reference's layout; a code cache's are dequantised)."""
+        self._no_tuple("to_tuple")
         return tuple(t.clone(memory_format=torch.contiguous_format) for t in self)
 
     def clone(self):
-        c = PackedKVCache(self.bs, self.nkv, self.hd, self.dtype, self.device, 0, code_bits=self.code_bits)
+        c = PackedKVCache(self.bs, self.nkv, self.hd, self.dtype, self.device, 0, code_bits=self.code_bits, ragged=self.ragged)
         c._allocate(self.capacity, keep=self)
         c.length = self.length
+        if self.ragged:
+            c.lengths.copy_(self.lengths)
         return c

@@ -303,9 +303,15 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
                     ln1=self.input_layernorm, ln2=self.post_attention_layernorm)
 
     def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None,
-                output_attentions=False, use_cache=False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                output_attentions=False, use_cache=False, new_tokens=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """new_tokens (packed blocks with a ragged PackedKVCache as past_key_value only): the valid rows of this right-padded
+        step per sequence, a Python sequence of ints or an int32 [bs] device tensor with 0 <= n_b <= T; None: all T."""
         if self.__dict__.get("_oq_packed") is not None:
-            return self._packed_forward(hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache)
+            return self._packed_forward(hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache,
+                                        new_tokens)
+        if new_tokens is not None:
+            from ._capi import OQError
+            raise OQError("new_tokens needs a packed block and a ragged PackedKVCache as past_key_value")
         hidden_states, back = self._enter(hidden_states)
         residual = hidden_states
         a = self.self_attn
@@ -337,29 +343,32 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         return (self._leave(hidden_states, back),)
 
     @torch.no_grad()
-    def _packed_forward(self, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache):
+    def _packed_forward(self, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache,
+                        new_tokens=None):
         """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
         in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual).  With a KV cache (past_key_value or use_cache;
         models/int_llama_layer.py:121-135,177,264-265) q / k are rotated at their positions and k / v appended to the cache in one
-        launch, then attention runs over the whole cache.  Returns (hidden,) plus (present,) -- a PackedKVCache -- when use_cache."""
+        launch, then attention runs over the whole cache.  Returns (hidden,) plus (present,) -- a PackedKVCache -- when use_cache.
+        A ragged PackedKVCache as past_key_value (one length per sequence, right-padded steps, new_tokens): _cached_attention."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if self.__dict__["_oq_packed"].get("act_quant"):
-            return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache)
+            return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens)
         x, back = self._enter(hidden_states)
         a, m = self.self_attn, self.mlp
         bsz, T, _ = x.shape
         nh, nkv, hd = a.num_heads, a.num_key_value_heads, a.head_dim
+        counts = self._new_tokens_in(new_tokens, past_key_value, bsz, T, x.device)
         cache = None
         if past_key_value is not None or use_cache:
             cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x)
-            pos = self._positions(position_ids, cache.length, bsz, T, x.device)
+            pos = self._step_positions(position_ids, cache, bsz, T, x.device)
             cos, sin = a._rope_table(cache.length + T, x.device)
         h = self.input_layernorm(x)
         q = a.q_proj(h).view(bsz, T, nh, hd)
         k = a.k_proj(h).view(bsz, T, nkv, hd)
         v = a.v_proj(h).view(bsz, T, nkv, hd)
         if cache is not None:
-            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos, new_tokens=counts)
         else:
             cos, sin = a._rope_tables(position_ids, T, x.device)
             q, k = ops.RopeFn.apply(q, cos, sin), ops.RopeFn.apply(k, cos, sin)
@@ -383,7 +392,7 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         return ops.act_codes(norm(x2), 4)
 
     @torch.no_grad()
-    def _packed_forward_a4(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache):
+    def _packed_forward_a4(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens=None):
         """W4A4 real-quant inference: norm -> 4-bit per-token codes (one set for q, k, v) -> integer q / k / v linears (fp32
         outputs: nothing is rounded to 16 bits in front of the head quantisers) -> RoPE + head quantisers (+ KV-cache append)
         in one launch -> attention on the quantised q / k / v -> codes -> integer o_proj (+ residual in its epilogue) -> norm
@@ -401,6 +410,7 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         if hd not in (64, 128):
             raise OQError(f"the W4A4 packed path covers head_dim 64 and 128 (oq_kv_append_quant), not {hd}")
         cd = x.dtype
+        counts = self._new_tokens_in(new_tokens, past_key_value, bsz, T, x.device)
         x2 = ops.cast(hidden_states, torch.float32).reshape(bsz * T, H)      # (exact widening of the caller's values)
         hint = self._norm_codes(self.input_layernorm, x2)
         f32 = torch.float32
@@ -411,9 +421,9 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         cache = None
         if past_key_value is not None or use_cache:
             cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x, head_bits=4)
-            pos = self._positions(position_ids, cache.length, bsz, T, x.device)
+            pos = self._step_positions(position_ids, cache, bsz, T, x.device)
             cos, sin = a._rope_table(cache.length + T, x.device)
-            attn = self._cached_attention(q, k, v, cache, attention_mask, scale, cos, sin, pos, head_bits=4)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, scale, cos, sin, pos, head_bits=4, new_tokens=counts)
         else:
             cos, sin = a._rope_tables(position_ids, T, x.device)
             qr, kr, vr = (torch.empty(t.shape, dtype=cd, device=x.device) for t in (q, k, v))

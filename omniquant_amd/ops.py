@@ -1622,9 +1622,22 @@ class LetVectorsFn(torch.autograd.Function):
         return tuple(pg) + tuple(res[7:]) + (None,) * 8
 
 
-def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, positions):
-    """What kv_append and kv_append_quant validate alike: the caches (None: no cache) against k, the row range, q, the cos / sin
-    tables and the positions.  Returns (cap, nh, P, pos_bstride, contiguous positions)."""
+def _ragged_lengths(fn, lengths, bs, device, past=0):
+    """Validate per-sequence lengths (kvcache.PackedKVCache(ragged=True).lengths): an int32 [bs] tensor on `device`, which
+    excludes a non-zero `past`.  Host checks of dtype, shape and device only: the values are never read."""
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (bs,):
+        what = f"{tuple(lengths.shape)} {lengths.dtype}" if torch.is_tensor(lengths) else type(lengths).__name__
+        raise C.OQError(f"{fn}: lengths must be an int32 [{bs}] tensor, got {what}")
+    if lengths.device != device:
+        raise C.OQError(f"{fn}: lengths on {lengths.device}, the cache on {device}")
+    if past:
+        raise C.OQError(f"{fn}: lengths (one past per sequence) excludes past = {past}")
+    return lengths.contiguous()
+
+
+def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, positions, lengths=None):
+    """What kv_append and kv_append_quant validate alike: the caches (None: no cache) against k, the row range (lengths: the
+    kernel guards it), q, the cos / sin tables and the positions.  Returns (cap, nh, P, pos_bstride, contiguous positions)."""
     bs, Tq, nkv, hd = k.shape
     cap = 0
     if k_cache is not None:
@@ -1633,7 +1646,7 @@ def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, 
                 or v_cache.dtype != cache_dtype:
             raise C.OQError(f"{fn}: cache {tuple(k_cache.shape)} {k_cache.dtype} does not fit k {tuple(k.shape)} {k.dtype}")
         cap = k_cache.shape[2]
-        if past < 0 or past + Tq > cap:
+        if lengths is None and (past < 0 or past + Tq > cap):
             raise C.OQError(f"{fn}: rows [{past}, {past + Tq}) beyond the capacity {cap}")
     nh = 0
     if q is not None:
@@ -1653,21 +1666,28 @@ def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, 
     return cap, nh, P, pbs, positions
 
 
-def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None):
+def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None, lengths=None):
     """Append one step's k / v [bs, Tq, nkv, hd] to rows [past, past + Tq) of the [bs, nkv, cap, hd] caches in ONE launch
     (csrc/oq_decode.hip), rotating q (into q_out) and k with the cos / sin tables [P, hd] (rows = positions 0..P-1) gathered at
     `positions` (int64 [1 | bs, Tq]; None = past + t).  cos None: no rotation (OPT).  k_out: optional [bs, Tq, nkv, hd] copy
-    of the rotated k (the prefill's attention reads it)."""
+    of the rotated k (the prefill's attention reads it).
+    lengths (ragged batches; past must be 0): int32 [bs] on the cache's device, one past per sequence, read by the kernel
+    only (oq_kv_append_ragged): sequence b's row t goes to cache row lengths[b] + t and, with positions None, rotates at that
+    position.  A row outside [0, cap) is not stored to the cache (the kernel guards what the host cannot see)."""
     bs, Tq, nkv, hd = k.shape
+    if lengths is not None:
+        lengths = _ragged_lengths("kv_append", lengths, bs, k_cache.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype:
         raise C.OQError(f"kv_append: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
-    cap, nh, P, pbs, positions = _kv_append_args("kv_append", k, v, k_cache, v_cache, k.dtype, past, q, cos, sin, positions)
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append", k, v, k_cache, v_cache, k.dtype, past, q, cos, sin, positions, lengths)
     if q is not None:
         q = q.contiguous()
         q_out = q if q_out is None else q_out
     k, v = k.contiguous(), v.contiguous()
-    C.call("oq_kv_append", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out), C.ptr(k_cache), C.ptr(v_cache), C.dt(k),
-           bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, C.stream())
+    ragged = lengths is not None
+    C.call("oq_kv_append_ragged" if ragged else "oq_kv_append", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out),
+           C.ptr(k_cache), C.ptr(v_cache), C.dt(k), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos),
+           C.fptr(sin), P, C.ptr(positions), pbs, C.stream())
     return q_out
 
 
@@ -1698,41 +1718,53 @@ def _code_buffers(fn, k_codes, v_codes, k_meta, v_meta, bs, nkv, hd):
 
 
 def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q=None, q_out=None, k_out=None, v_out=None,
-                    cos=None, sin=None, positions=None):
+                    cos=None, sin=None, positions=None, lengths=None):
     """kv_append_quant on the 4-bit grid with a code cache as the destination (csrc/oq_decode.hip, oq_kv_append_quant_codes):
     rows [past, past + Tq) of k_codes / v_codes (uint8 [bs, nkv, cap, hd // 2]) receive the quantiser's codes and k_meta /
     v_meta (float32 [bs, nkv, cap, 2]) its (scale, zero-point); (code - zp) * scale is, bit for bit, what kv_append_quant
-    writes to a float32 cache.  q_out / k_out / v_out receive the fake-quant values in out_dtype as they do there."""
+    writes to a float32 cache.  q_out / k_out / v_out receive the fake-quant values in out_dtype as they do there.
+    lengths: as in kv_append (oq_kv_append_quant_codes_ragged)."""
     bs, Tq, nkv, hd = k.shape
+    if lengths is not None:
+        lengths = _ragged_lengths("kv_append_codes", lengths, bs, k_codes.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_codes: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
     _, nh, P, pbs, positions = _kv_append_args("kv_append_codes", k, v, None, None, out_dtype, past, q, cos, sin, positions)
     cap = _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd)
-    if past < 0 or past + Tq > cap:
+    ragged = lengths is not None
+    if not ragged and (past < 0 or past + Tq > cap):
         raise C.OQError(f"kv_append_codes: rows [{past}, {past + Tq}) beyond the capacity {cap}")
     if (k_out is None) != (v_out is None):
         raise C.OQError("kv_append_codes: k_out and v_out go together")
     q, k, v = _kv_quant_outs("kv_append_codes", q, k, v, out_dtype, q_out, k_out, v_out)
-    C.call("oq_kv_append_quant_codes", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
-           C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past),
-           C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4, C.stream())
+    C.call("oq_kv_append_quant_codes_ragged" if ragged else "oq_kv_append_quant_codes", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k),
+           C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype],
+           bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4,
+           C.stream())
     return q_out
 
 
 def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, q=None, q_out=None, k_out=None, v_out=None,
-                    cos=None, sin=None, positions=None):
+                    cos=None, sin=None, positions=None, lengths=None):
     """kv_append for the W4A4 packed blocks (csrc/oq_decode.hip, oq_kv_append_quant): q / k / v [bs, Tq, heads, hd] in float32
     or out_dtype are rotated (q, k; cos None: no rotation) exactly as kv_append rotates them, from fp32, then quantised per
     (token, head) over hd on the nbits asymmetric grid; the fake-quant values go, in out_dtype, to q_out, to cache rows
-    [past, past + Tq) and to k_out / v_out.  The caches may be None (the no-cache forward: k_out and v_out then)."""
+    [past, past + Tq) and to k_out / v_out.  The caches may be None (the no-cache forward: k_out and v_out then).
+    lengths: as in kv_append (oq_kv_append_quant_ragged; it needs the caches)."""
     bs, Tq, nkv, hd = k.shape
+    if lengths is not None:
+        if k_cache is None:
+            raise C.OQError("kv_append_quant: lengths without a cache")
+        lengths = _ragged_lengths("kv_append_quant", lengths, bs, k_cache.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_quant: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
-    cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, k_cache, v_cache, out_dtype, past, q, cos, sin, positions)
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, k_cache, v_cache, out_dtype, past, q, cos, sin, positions,
+                                                 lengths)
     q, k, v = _kv_quant_outs("kv_append_quant", q, k, v, out_dtype, q_out, k_out, v_out)
-    C.call("oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache),
-           C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap, int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs,
-           int(nbits), C.stream())
+    ragged = lengths is not None
+    C.call("oq_kv_append_quant_ragged" if ragged else "oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out),
+           C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache), C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap,
+           C.ptr(lengths) if ragged else int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, int(nbits), C.stream())
     return q_out
 
 
@@ -1752,6 +1784,16 @@ def act_codes(x2, nbits, out=None):
     return IntCodes(codes, vec[0], vec[1], vec[2], int(nbits))
 
 
+def _ragged_decode_args(fn, lengths, bs, device, mask, Tq, L, cap):
+    """The lengths of a ragged decode attention, validated (they replace the mask: each query row sees its own past), and the
+    bound L the launches are planned with."""
+    if mask is not None:
+        raise C.OQError(f"{fn}: lengths excludes a mask (row t of sequence b attends rows <= lengths[b] + t)")
+    if not Tq <= int(L) <= cap:
+        raise C.OQError(f"{fn}: the bound L = {L} of lengths + Tq must lie in [Tq = {Tq}, capacity = {cap}]")
+    return _ragged_lengths(fn, lengths, bs, device)
+
+
 def _decode_mask(fn, mask, bs, Tq, L):
     """The additive mask of a decode attention as (tensor kept alive, pointer, dtype, batch stride, row stride)."""
     if mask is None:
@@ -1764,16 +1806,19 @@ def _decode_mask(fn, mask, bs, Tq, L):
             mask.stride(2) if Tq > 1 else 0)
 
 
-def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=None):
+def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=None, lengths=None):
     """decode_attention over a 4-bit code cache (csrc/oq_decode.hip, oq_attn_decode_codes): `cache` is a PackedKVCache with
     code_bits 4 or the (k_codes, v_codes, k_meta, v_meta) buffers; K and V are dequantised in registers as (code - zp) * scale.
-    Same scores, softmax, mask handling, split plan and reproducibility as decode_attention; q and o in the compute dtype."""
+    Same scores, softmax, mask handling, split plan and reproducibility as decode_attention; q and o in the compute dtype.
+    lengths: as in decode_attention (oq_attn_decode_codes_ragged)."""
     bs, Tq, nh, hd = q.shape
     bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
     if len(bufs) != 4 or bufs[0].dim() != 4 or bufs[0].shape[0] != bs:
         raise C.OQError(f"decode_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
     nkv = bufs[0].shape[1]
     cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd)
+    if lengths is not None:
+        lengths = _ragged_decode_args("decode_attention_codes", lengths, bs, bufs[0].device, mask, Tq, L, cap)
     if q.dtype not in (torch.float32, torch.bfloat16):
         raise C.OQError(f"decode_attention_codes: q {q.dtype} (float32 or bfloat16)")
     q = q.contiguous()
@@ -1782,27 +1827,41 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
     if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
     o = torch.empty_like(q) if out is None else out
+    if lengths is not None:
+        C.call("oq_attn_decode_codes_ragged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+               C.dt(q), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
+               workspace.numel() * workspace.element_size(), C.stream())
+        return o
     C.call("oq_attn_decode_codes", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
            bs, Tq, nh, nkv, hd, cap, int(L), float(scale), mptr, mdt, mbs, mld, C.ptr(workspace),
            workspace.numel() * workspace.element_size(), C.stream())
     return o
 
 
-def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None):
+def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None, lengths=None):
     """o [bs, Tq, nh, hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over the first L rows of the [bs, nkv, cap, hd]
     caches (csrc/oq_decode.hip: split-L streaming, fp32 online softmax, one rounding).  mask: None or additive [bs | 1, 1, Tq, L]
-    in float32 / float16 / bfloat16, read in place on the device (any batch / row stride; a batch of 1 is broadcast)."""
+    in float32 / float16 / bfloat16, read in place on the device (any batch / row stride; a batch of 1 is broadcast).
+    lengths (ragged batches; mask must be None): int32 [bs] on the caches' device = the rows of each sequence BEFORE this step's
+    append, read by the kernel only (oq_attn_decode_ragged).  L is then an upper bound of lengths[b] + Tq over the batch, L <= cap
+    (launches and workspace depend on it, never on the values); query row t of sequence b attends rows j <= lengths[b] + t."""
     bs, Tq, nh, hd = q.shape
     if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
             or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise C.OQError(f"decode_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
     nkv, cap = k_cache.shape[1], k_cache.shape[2]
+    if lengths is not None:
+        lengths = _ragged_decode_args("decode_attention", lengths, bs, k_cache.device, mask, Tq, L, cap)
     q = q.contiguous()
     mask, mptr, mdt, mbs, mld = _decode_mask("decode_attention", mask, bs, Tq, L)
     ws_n = C.size_call("oq_attn_decode_workspace", bs, nh, nkv, Tq, int(L), hd)
     if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
     o = torch.empty_like(q) if out is None else out
+    if lengths is not None:
+        C.call("oq_attn_decode_ragged", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd, cap,
+               C.ptr(lengths), int(L), float(scale), C.ptr(workspace), workspace.numel() * workspace.element_size(), C.stream())
+        return o
     C.call("oq_attn_decode", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd, cap, int(L),
            float(scale), mptr, mdt, mbs, mld, C.ptr(workspace), workspace.numel() * workspace.element_size(), C.stream())
     return o

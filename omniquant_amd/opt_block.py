@@ -95,7 +95,11 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
     def forward(self, hidden_states, attention_mask=None, layer_head_mask=None, output_attentions=False,
                 use_cache=False, past_key_value=None, **kwargs) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         if self.__dict__.get("_oq_packed") is not None:
-            return self._packed_forward(hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value)
+            return self._packed_forward(hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value,
+                                        kwargs.get("new_tokens"))
+        if kwargs.get("new_tokens") is not None:
+            from ._capi import OQError
+            raise OQError("new_tokens needs a packed block and a ragged PackedKVCache as past_key_value")
         if use_cache or output_attentions:
             raise NotImplementedError("the calibration hot path runs without KV cache / attention outputs")
         hidden_states, back = self._enter(hidden_states)
@@ -134,8 +138,11 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         return (self._leave(hidden_states, back),)
 
     @torch.no_grad()
-    def _packed_forward(self, hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value):
-        """Real-quant inference (realquant.pack_block): the same block with LayerNorm, biased PackedLinears and ReLU."""
+    def _packed_forward(self, hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value,
+                        new_tokens=None):
+        """Real-quant inference (realquant.pack_block): the same block with LayerNorm, biased PackedLinears and ReLU.
+        new_tokens (the keyword of forward's **kwargs): the valid rows per sequence of a right-padded step on a ragged
+        PackedKVCache (_cached_attention)."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if layer_head_mask is not None:
             raise NotImplementedError("the packed inference path runs without head masks")
@@ -144,6 +151,7 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         bsz, T, _ = x.shape
         nh, hd = a.num_heads, a.head_dim
         cached = past_key_value is not None or use_cache
+        counts = self._new_tokens_in(new_tokens, past_key_value, bsz, T, x.device)
         # (KV-cache path, models/int_opt_layer.py:110-121,343-344: k / v appended to a PackedKVCache, returned as present)
         cache = self._kv_cache_in(past_key_value, bsz, T, nh, hd, x) if cached else None
         h = self.self_attn_layer_norm(x) if self.do_layer_norm_before else x
@@ -151,7 +159,7 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         k = a.k_proj(h).view(bsz, T, nh, hd)
         v = a.v_proj(h).view(bsz, T, nh, hd)
         if cached:
-            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0, new_tokens=counts)
         else:
             attn = self._packed_attention(q, k, v, attention_mask, 1.0)
         x = a.out_proj(attn.reshape(bsz, T, self.embed_dim), residual=x)

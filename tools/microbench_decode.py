@@ -16,7 +16,16 @@
    and maximum of each kernel, the bf16 kernel's own run-to-run spread (max - min over its median) and the ratio of the
    medians.
 
-usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N] [--codes [--rounds 7]]
+4. `--ragged`: instead of 1 and 2, a batch of 8 sequences of lengths 128 ... 8192 (geometric) at the 7B shape, Tq = 1, on a
+   bf16 cache and on a 4-bit code cache: oq_attn_decode_ragged / oq_attn_decode_codes_ragged (per-sequence lengths on the
+   device, bound 8192, no mask) against oq_attn_decode / oq_attn_decode_codes on the same batch left-padded to 8192 with a
+   transformers-style fp16 mask.  Same buffers, same process, cold cache sets (one round over the sets reads more than the
+   Infinity Cache even for the ragged kernel, which reads the fewest bytes); the four graphs are replayed alternately
+   `--rounds` times.  A row reports median / min / max per kernel, the bytes each must read, the run-to-run spread (max -
+   min over the median) of both bf16 kernels and the ratios of the medians.
+
+usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
+                                         [--codes | --ragged [--rounds 7]]
 """
 import argparse
 import json
@@ -55,6 +64,35 @@ def timed(fns, reps):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1000.0 / (reps * len(fns))
+
+
+def interleaved(launch_lists, reps, rounds):
+    """Time several kernels against each other in one process: each list of launches (one per cold cache set) is warmed up and
+    captured as one graph of `reps` rounds, then the graphs are replayed alternately `rounds` times under hipEvents.  Returns
+    (per-launch microseconds of every replay, per list; their medians)."""
+    graphs = []
+    for fns in launch_lists:
+        for f in fns:
+            f()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(reps):
+                for f in fns:
+                    f()
+        g.replay()
+        torch.cuda.synchronize()
+        graphs.append((g, reps * len(fns)))
+    us = [[] for _ in graphs]
+    for _ in range(rounds):
+        for i, (g, n) in enumerate(graphs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            us[i].append(a.elapsed_time(b) * 1000.0 / n)
+    return us, [sorted(u)[len(u) // 2] for u in us]
 
 
 def kernel_rows(reps, quick, dev):
@@ -125,30 +163,9 @@ def codes_rows(reps, rounds, quick, dev):
                 csets = [(torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev),
                           torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev), meta(), meta())
                          for _ in range(max(2, -(-COLD_BYTES // code_bytes)))]
-                graphs = []
-                for fns in ([(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)) for s in fsets],
-                            [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in csets]):
-                    for f in fns:
-                        f()
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        for _ in range(reps):
-                            for f in fns:
-                                f()
-                    g.replay()
-                    torch.cuda.synchronize()
-                    graphs.append((g, reps * len(fns)))
-                us = ([], [])
-                for _ in range(rounds):
-                    for i, (g, n) in enumerate(graphs):
-                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        a.record()
-                        g.replay()
-                        b.record()
-                        torch.cuda.synchronize()
-                        us[i].append(a.elapsed_time(b) * 1000.0 / n)
-                med = [sorted(u)[len(u) // 2] for u in us]
+                us, med = interleaved(
+                    ([(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)) for s in fsets],
+                     [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in csets]), reps, rounds)
                 r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, L=L, Tq=1, dtype="bfloat16", cache="cold", rounds=rounds,
                          bf16_sets=len(fsets), code_sets=len(csets),
                          bf16_us=med[0], bf16_us_min=min(us[0]), bf16_us_max=max(us[0]),
@@ -159,9 +176,66 @@ def codes_rows(reps, rounds, quick, dev):
                          codes_frac_hbm=code_bytes / med[1] * 1e6 / HBM_BPS)
                 rows.append(r)
                 print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
-                del fsets, csets, graphs
+                del fsets, csets
                 torch.cuda.empty_cache()
     return rows
+
+
+RAGGED_LENGTHS = [128, 232, 420, 760, 1378, 2496, 4522, 8192]      # a batch of 8, geometric from 128 to 8192
+
+
+def ragged_bytes(lengths, nkv, hd):
+    """Bytes of K and V each kernel must read for one step of the batch: (bf16 ragged, bf16 padded, codes ragged, codes
+    padded).  The padded kernels stream every sequence at the longest length, and their fp16 mask on top."""
+    bs, Lmax, rows = len(lengths), max(lengths), sum(lengths)
+    mask = bs * Lmax * 2
+    return (2 * nkv * rows * hd * 2, 2 * nkv * bs * Lmax * hd * 2 + mask,
+            2 * nkv * rows * (hd // 2 + 8), 2 * nkv * bs * Lmax * (hd // 2 + 8) + mask)
+
+
+def ragged_rows(reps, rounds, dev):
+    name, nh, nkv, hd = SHAPES[0]
+    lengths = RAGGED_LENGTHS
+    bs, L = len(lengths), max(lengths)
+    need = ragged_bytes(lengths, nkv, hd)
+    scale = hd ** -0.5
+    q = torch.randn(bs, 1, nh, hd, device=dev).bfloat16()
+    o = torch.empty_like(q)
+    ws = torch.empty(C.size_call("oq_attn_decode_workspace", bs, nh, nkv, 1, L, hd), dtype=torch.uint8, device=dev)
+    lens = torch.tensor([n - 1 for n in lengths], dtype=torch.int32, device=dev)      # the rows before this step's append
+    # the padded form of the batch: sequence b occupies the LAST lengths[b] rows, the mask hides the pad rows in front
+    mask = torch.zeros(bs, 1, 1, L, dtype=torch.float16, device=dev)
+    for b, n in enumerate(lengths):
+        mask[b, 0, 0, :L - n] = torch.finfo(torch.float16).min
+    fsets = [(torch.randn(bs, nkv, L, hd, device=dev).bfloat16(), torch.randn(bs, nkv, L, hd, device=dev).bfloat16())
+             for _ in range(max(2, -(-COLD_BYTES // need[0])))]
+
+    def meta():
+        m = torch.empty(bs, nkv, L, 2, device=dev)
+        m[..., 0] = torch.rand(bs, nkv, L, device=dev) * 0.1 + 0.3
+        m[..., 1] = torch.randint(5, 11, (bs, nkv, L), device=dev).float()
+        return m
+
+    csets = [(torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev),
+              torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev), meta(), meta())
+             for _ in range(max(2, -(-COLD_BYTES // need[2])))]
+    kinds = ("bf16_ragged", "bf16_padded", "codes_ragged", "codes_padded")
+    launches = ([(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws, lengths=lens)) for s in fsets],
+                [(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, mask, out=o, workspace=ws)) for s in fsets],
+                [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws, lengths=lens)) for s in csets],
+                [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, mask, out=o, workspace=ws)) for s in csets])
+    us, med = interleaved(launches, reps, rounds)
+    r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, lengths=lengths, L_bound=L, Tq=1, dtype="bfloat16", cache="cold",
+             rounds=rounds, bf16_sets=len(fsets), code_sets=len(csets))
+    for i, k in enumerate(kinds):
+        r.update({k + "_us": med[i], k + "_us_min": min(us[i]), k + "_us_max": max(us[i]), k + "_bytes": need[i],
+                  k + "_GBps": need[i] / med[i] / 1e3})
+    r.update(bf16_ragged_spread=(max(us[0]) - min(us[0])) / med[0], bf16_padded_spread=(max(us[1]) - min(us[1])) / med[1],
+             bf16_ragged_over_padded=med[0] / med[1],
+             codes_ragged_over_padded=med[2] / med[3], bf16_bytes_ragged_over_padded=need[0] / need[1],
+             codes_bytes_ragged_over_padded=need[2] / need[3])
+    print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+    return [r]
 
 
 def packed_7b_block(dev, L_cap):
@@ -262,7 +336,8 @@ def main():
     ap.add_argument("--step-only", action="store_true", help="only N eager decode steps of the 7B block (for rocprofv3)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--codes", action="store_true", help="the code-cache kernel interleaved with the bf16-cache kernel")
-    ap.add_argument("--rounds", type=int, default=7, help="--codes: alternating replays of the two graphs")
+    ap.add_argument("--ragged", action="store_true", help="ragged-batch kernels interleaved with the padded, masked ones")
+    ap.add_argument("--rounds", type=int, default=7, help="--codes / --ragged: alternating replays of the graphs")
     a = ap.parse_args()
     dev = "cuda:0"
     if not torch.cuda.is_available():
@@ -271,7 +346,9 @@ def main():
     if a.step_only:
         block_step(dev, a.reps, steps_only=a.steps)
         return
-    if a.codes:
+    if a.ragged:
+        rows = ragged_rows(a.reps, a.rounds, dev)
+    elif a.codes:
         rows = codes_rows(a.reps, a.rounds, a.quick, dev)
     else:
         rows = kernel_rows(a.reps, a.quick, dev)
