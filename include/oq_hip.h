@@ -411,8 +411,45 @@ int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, const void* 
                                 void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
                                 const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes,
                                 void* stream);
+/*   Paged storage: the ragged entry points with (table, max_pages, num_pages, page_size) in the place of cap.  The cache
+ *      buffers are page pools: k / v [num_pages, nkv, PS, hd], codes uint8 [num_pages, nkv, PS, hd / 2] and meta f32
+ *      [num_pages, nkv, PS, 2], PS = page_size one of 16, 32, 64, 128 (row format, nibble order and value contract as above).
+ *      table int32 [bs, max_pages], contiguous, on the device: logical row j of sequence b, kv head h, is pool row
+ *      (table[b * max_pages + j / PS] * nkv + h) * PS + j % PS, so the PS rows of one (page, kv head) are contiguous.  The
+ *      host reads neither lens nor table (both 4-byte aligned); num_pages > 0, max_pages > 0.
+ *   oq_kv_append_paged / oq_kv_append_quant_paged / oq_kv_append_quant_codes_paged: step row t of sequence b goes to logical
+ *      row lens[b] + t and, with pos == NULL, rotates there.  A row is not stored (skipped, never clamped onto another row)
+ *      when lens[b] + t lies outside [0, max_pages * PS) -- its table entry is then not read -- or when its table entry lies
+ *      outside [0, num_pages); q_out / k_out / v_out are complete.  The bytes stored for a row are those the _ragged entry
+ *      point stores.  The pools are required.
+ *   oq_attn_decode_paged / oq_attn_decode_codes_paged: Tq <= L_bound <= max_pages * PS.  Lengths are clamped as in the ragged
+ *      form, table entries of rows >= lens[b] + Tq are never read and such rows never loaded; a row whose entry lies outside
+ *      [0, num_pages) is invisible and not loaded (a query row that sees no row at all comes out as NaN).  Split plan, workspace
+ *      (oq_attn_decode_workspace with L = L_bound) and every sum are the ragged form's: on the same rows, lens and L_bound the
+ *      output equals oq_attn_decode_ragged's / oq_attn_decode_codes_ragged's bit for bit, for every page size and page order. */
+int oq_kv_append_paged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_pool, void* v_pool, int dtype,
+                       int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages,
+                       int page_size, const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                       int64_t pos_bstride, void* stream);
+int oq_kv_append_quant_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                             void* k_pool, void* v_pool, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                             const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens,
+                             const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits,
+                             void* stream);
+int oq_kv_append_quant_codes_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                                   void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq,
+                                   int nh, int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages,
+                                   int page_size, const int32_t* lens, const float* cos, const float* sin, int64_t P,
+                                   const int64_t* pos, int64_t pos_bstride, int nbits, void* stream);
+int oq_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
+                         int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                         const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_attn_decode_codes_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                               void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                               int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
+                               float scale, void* workspace, int64_t workspace_bytes, void* stream);
 
-/* ---- fused causal attention (models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
+/* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,
  *      as quant_x1/quant_x2 do in the reference); lse [bs,nh,T] f32 (log2 domain) is written by fwd and read by bwd.

@@ -91,6 +91,17 @@ SIGNATURES = {
     "oq_attn_decode_ragged": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
     "oq_attn_decode_codes_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp,
                                     _i64, _vp],
+    # paged storage: (table, max_pages, num_pages, page_size) in the place of the ragged forms' cap
+    "oq_kv_append_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp,
+                           _i64, _vp, _i64, _vp],
+    "oq_kv_append_quant_paged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64,
+                                 _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "oq_kv_append_quant_codes_paged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32,
+                                       _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "oq_attn_decode_paged": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _f32, _vp,
+                             _i64, _vp],
+    "oq_attn_decode_codes_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
+                                   _i64, _f32, _vp, _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,

@@ -69,15 +69,16 @@ class QuantBlockMixin:
         blocks, whose cache holds head-quantised k / v): the tuple's raw rows are quantised once, on import.
         A block packed with kv_cache_bits=4 creates, and converts tuples into, 4-bit code caches; a caller's PackedKVCache of
         either kind is taken as it is (an empty pre-sized code cache switches an unmarked W4A4 block to codes), except that a
-        code cache needs the head quantisers (head_bits 4)."""
+        code cache needs the head quantisers (head_bits 4).  So is a caller's PagedKVCache (paged, ragged storage); a block never
+        creates one by itself."""
         from ._capi import OQError
-        from .kvcache import PackedKVCache
+        from .kvcache import PackedKVCache, PagedKVCache
         if hd not in (64, 128):
             raise OQError(f"KV-cache decoding covers head_dim 64 and 128 (oq_attn_decode), not {hd}")
         code_bits = self.__dict__["_oq_packed"].get("kv_cache_bits")
         if past_key_value is None:
             return PackedKVCache(bsz, nkv, hd, x.dtype, x.device, Tq, code_bits=code_bits)
-        if isinstance(past_key_value, PackedKVCache):
+        if isinstance(past_key_value, (PackedKVCache, PagedKVCache)):
             c = past_key_value
             if (c.bs, c.nkv, c.hd) != (bsz, nkv, hd) or c.dtype != x.dtype or c.device != x.device:
                 raise OQError(f"{c!r} does not fit this block's step: batch {bsz}, {nkv} kv heads of {hd}, {x.dtype} on {x.device}")
@@ -90,31 +91,33 @@ class QuantBlockMixin:
                 raise OQError(f"past_key_value {tuple(getattr(k, 'shape', ()))}: expected [{bsz}, {nkv}, T, {hd}]")
             return PackedKVCache.from_tuple(past_key_value, dtype=x.dtype, capacity=k.shape[2] + Tq, head_bits=head_bits,
                                             code_bits=code_bits)
-        raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple or a PackedKVCache")
+        raise OQError(f"past_key_value of type {type(past_key_value).__name__}: expected None, a (k, v) tuple, a PackedKVCache or a "
+                      "PagedKVCache")
 
     @staticmethod
     def _new_tokens_in(new_tokens, past_key_value, bsz, T, device):
         """new_tokens (the valid step rows per sequence of a right-padded ragged step) as (int32 [bs] device tensor or None,
-        what the cache's host bound grows by).  None: all T rows.  A Python sequence of ints is checked (0 <= n <= T) and
-        uploaded, and the bound grows by its maximum; a device tensor is taken as it is -- its values are never read -- and
-        the bound grows by T.  Without a ragged PackedKVCache as past_key_value it is refused."""
+        what the cache's host bound grows by, the counts as Python ints or None).  None: all T rows.  A Python sequence of ints
+        is checked (0 <= n <= T) and uploaded, and the bound grows by its maximum; a device tensor is taken as it is -- its
+        values are never read -- and the bound grows by T.  Without a ragged cache (PackedKVCache(ragged=True) or a
+        PagedKVCache) as past_key_value it is refused."""
         from ._capi import OQError
         if new_tokens is None:
-            return None, T
+            return None, T, None
         if not getattr(past_key_value, "ragged", False):
             raise OQError("new_tokens needs a ragged PackedKVCache as past_key_value (PackedKVCache(..., ragged=True))")
         if torch.is_tensor(new_tokens):
             if new_tokens.dtype != torch.int32 or tuple(new_tokens.shape) != (bsz,) or new_tokens.device != device:
                 raise OQError(f"new_tokens: expected an int32 [{bsz}] tensor on {device}, got {tuple(new_tokens.shape)} "
                               f"{new_tokens.dtype} on {new_tokens.device}")
-            return new_tokens, T
+            return new_tokens, T, None
         try:
             seq = [new_tokens[i].__index__() for i in range(len(new_tokens))]
         except (TypeError, AttributeError):
             raise OQError(f"new_tokens: expected {bsz} ints or an int32 [{bsz}] device tensor, got {new_tokens!r}") from None
         if len(seq) != bsz or min(seq) < 0 or max(seq) > T:
             raise OQError(f"new_tokens {seq}: one count in [0, {T}] for each of the {bsz} sequences")
-        return torch.tensor(seq, dtype=torch.int32).to(device, non_blocking=True), max(seq)
+        return torch.tensor(seq, dtype=torch.int32).to(device, non_blocking=True), max(seq), seq
 
     @staticmethod
     def _positions(position_ids, past, bsz, T, device):
@@ -134,7 +137,7 @@ class QuantBlockMixin:
         return self._positions(position_ids, cache.length, bsz, T, device)
 
     def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None, head_bits=None,
-                          new_tokens=(None, None)):
+                          new_tokens=(None, None, None)):
         """Attention of this step's q [bs, Tq, nh, hd] over the cache plus this step's k / v, which are appended to it (rotated
         by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
         (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation.
@@ -144,18 +147,23 @@ class QuantBlockMixin:
         oq_attn_decode_codes on them; its prefill runs the same attention launches on the same q / k / v values.
         A ragged cache (cache.ragged): the append and the attention read the same pre-step cache.lengths on the device
         (lengths= of the ops), `past` and L are host bounds, and the step's rows are right-padded: new_tokens = (counts or None
-        for all Tq, growth of the bound) from _new_tokens_in says how many rows of each sequence count.  All Tq rows are
+        for all Tq, growth of the bound, the counts on the host or None) from _new_tokens_in says how many rows of each sequence
+        count.  All Tq rows are
         written; rows at or beyond a sequence's new length are scratch that its next step overwrites, and the outputs of pad
         query rows are finite and unspecified.  With cache.length == 0 this is the prefill above (the caller's causal mask
         keeps right padding away from the valid rows; the append goes at lengths = 0).  With a past the mask must be None
         (row t of sequence b attends rows <= lengths[b] + t) and positions None leaves them to the kernel (lengths[b] + t).
-        A decode step on a ragged cache performs no device-to-host read and builds no mask or position tensor."""
+        A decode step on a ragged cache performs no device-to-host read and builds no mask or position tensor.
+        A paged cache (cache.paged, always ragged; kvcache.PagedKVCache): the same ops calls on its page pools with
+        page_table=cache.page_table; reserve() gives every sequence the pages the step's rows need (uploading the table only
+        if one was added) and advance() books the step in the cache's host bounds.  Nothing else about the step changes."""
         from . import ops
         from ._capi import OQError
         bsz, Tq = q.shape[0], q.shape[1]
         past = cache.length
         L = past + Tq
         lens = cache.lengths if cache.ragged else None
+        paged = {"page_table": cache.page_table} if getattr(cache, "paged", False) else {}
         if lens is not None and past > 0 and attention_mask is not None:
             raise OQError("a ragged cache with a past takes no attention_mask: each sequence attends its own rows "
                           "(pass attention_mask=None)")
@@ -169,17 +177,18 @@ class QuantBlockMixin:
             qr = torch.empty_like(q) if rot else q
             kr, vr = torch.empty_like(k) if (rot and past == 0) else None, None
             ops.kv_append(k, v, cache.k, cache.v, 0 if cache.ragged else past, q=q if rot else None, q_out=qr if rot else None,
-                          k_out=kr, cos=cos, sin=sin, positions=positions, lengths=lens)
+                          k_out=kr, cos=cos, sin=sin, positions=positions, lengths=lens, **paged)
         else:
             qr = torch.empty(q.shape, dtype=cache.dtype, device=q.device)
             kr, vr = (torch.empty(k.shape, dtype=cache.dtype, device=q.device) for _ in range(2)) if past == 0 else (None, None)
             if cache.code_bits is not None:
                 ops.kv_append_codes(k, v, cache.dtype, cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta,
                                     past=0 if cache.ragged else past, q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin,
-                                    positions=positions, lengths=lens)
+                                    positions=positions, lengths=lens, **paged)
             else:
                 ops.kv_append_quant(k, v, head_bits, cache.dtype, k_cache=cache.k, v_cache=cache.v, past=0 if cache.ragged else past,
-                                    q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions, lengths=lens)
+                                    q=q, q_out=qr, k_out=kr, v_out=vr, cos=cos, sin=sin, positions=positions, lengths=lens,
+                                    **paged)
         if lens is None:
             cache.length = L
         if past == 0:
@@ -188,14 +197,16 @@ class QuantBlockMixin:
                 mask = mask.expand(bsz, 1, Tq, L)
             attn = self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
         elif cache.code_bits is not None:
-            attn = ops.decode_attention_codes(qr, cache, L, scale, attention_mask, lengths=lens)
+            attn = ops.decode_attention_codes(qr, cache, L, scale, attention_mask, lengths=lens, **paged)
         else:
-            attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask, lengths=lens)
+            attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask, lengths=lens, **paged)
         if lens is not None:
             # (after the attention, which reads the pre-step lengths; the stream orders the launches)
-            counts, grow = new_tokens
+            counts, grow, host_counts = new_tokens
             lens.add_(Tq if counts is None else counts)
             cache.length = past + (Tq if grow is None else grow)
+            if paged:
+                cache.advance(Tq, host_counts, exact=counts is None or host_counts is not None)
         return attn
 
     @staticmethod

@@ -16,6 +16,16 @@
 
 namespace {
 
+// Paged storage: the rows of a cache live in pages of PS = 1 << lg rows per kv head, pool buffers [num_pages, nkv, PS, ...],
+// and logical row j of sequence b is row j & (PS - 1) of page table[b * max_pages + (j >> lg)].  table == NULL: the contiguous
+// [bs, nkv, cap, ...] slab.  The host never reads the table, so the kernels guard its entries: a row whose entry lies outside
+// [0, num_pages) is neither stored (append) nor loaded (attention, where it counts as invisible).
+struct PageMap {
+    const int32_t* table;               // int32 [bs, max_pages] on the device
+    int64_t max_pages, num_pages;
+    int lg;
+};
+
 // ---- KV append: q [bs,Tq,nh,hd], k / v [bs,Tq,nkv,hd] -> rotated q (q_out), rotated k (cache rows past.., and k_out),
 //      plain v (cache, and v_out).  One work item = 8 elements of a head's first half and the 8 partners of its second half.
 //      QUANT (W4A4 packed blocks): the rotation runs on the fp32 inputs, then the per-(token, head) asymmetric quantiser over
@@ -41,13 +51,18 @@ struct AppendP {
     float *k_meta, *v_meta;
     // RAGGED instantiations: the rows before this step, per sequence, int32 [bs] on the device (`past` is not read)
     const int32_t* lens;
+    // PAGED instantiations: where logical row lens[b] + t lives (cap = max_pages * PS)
+    PageMap pm;
 };
 
 // RAGGED: sequence b's row t goes to cache row lens[b] + t (and rotates at that position when pos == NULL).  The host cannot
 // see lens, so the kernel guards the range itself: a row outside [0, cap) is not stored to the cache / codes / meta (skipped,
 // never clamped onto another row); its q_out / k_out / v_out rows are written like any other.
-template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED>
+// PAGED (a form of RAGGED): that logical row goes through the page table; a row whose table entry is outside [0, num_pages)
+// is skipped in the same way (the entry of a row outside [0, cap) is not read).
+template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED, bool PAGED>
 __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
+    static_assert(RAGGED || !PAGED, "paged storage is always ragged");
     const int hd = p.hd, nh = p.nh, nkv = p.nkv;
     const int64_t Tq = p.Tq, cap = p.cap;
     int64_t past = p.past;
@@ -65,10 +80,23 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
         r /= nslot;
         const int64_t t = r % Tq, b = r / Tq;
         bool fits = true;
+        int64_t page = 0;
         if constexpr (RAGGED) {
             past = p.lens[b];
             fits = past + t >= 0 && past + t < cap;
         }
+        if constexpr (PAGED) {
+            if (fits) {
+                page = p.pm.table[b * p.pm.max_pages + ((past + t) >> p.pm.lg)];
+                fits = page >= 0 && page < p.pm.num_pages;
+            }
+            if (!fits) page = 0;
+        }
+        // the buffer row of kv head h that this step row goes to
+        auto crow = [&](int h) -> int64_t {
+            if constexpr (PAGED) return ((page * nkv + h) << p.pm.lg) + ((past + t) & ((int64_t(1) << p.pm.lg) - 1));
+            else return (b * nkv + h) * cap + past + t;
+        };
         const TIN* src;
         T* dst;
         T* dst2;
@@ -82,20 +110,20 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
         } else if (slot < nh + nkv) {
             const int h = slot - nh;
             src = k + ((b * Tq + t) * nkv + h) * hd;
-            dst = kc && fits ? kc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst = kc && fits ? kc + crow(h) * hd : nullptr;
             dst2 = k_out ? k_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
             if constexpr (CODES) {
-                cdst = fits ? p.k_codes + ((b * nkv + h) * cap + past + t) * half : nullptr;
-                mdst = p.k_meta + ((b * nkv + h) * cap + past + t) * 2;
+                cdst = fits ? p.k_codes + crow(h) * half : nullptr;
+                mdst = p.k_meta + crow(h) * 2;
             }
         } else {
             const int h = slot - nh - nkv;
             src = v + ((b * Tq + t) * nkv + h) * hd;
-            dst = vc && fits ? vc + ((b * nkv + h) * cap + past + t) * hd : nullptr;
+            dst = vc && fits ? vc + crow(h) * hd : nullptr;
             dst2 = v_out ? v_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
             if constexpr (CODES) {
-                cdst = fits ? p.v_codes + ((b * nkv + h) * cap + past + t) * half : nullptr;
-                mdst = p.v_meta + ((b * nkv + h) * cap + past + t) * 2;
+                cdst = fits ? p.v_codes + crow(h) * half : nullptr;
+                mdst = p.v_meta + crow(h) * 2;
             }
             rot = false;
         }
@@ -178,21 +206,22 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     }
 }
 
-template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED>
+template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED, bool PAGED>
 void launch_append(const AppendP& p, hipStream_t st) {
     const int64_t n = p.bs * p.Tq * (p.nh + 2 * p.nkv) * (p.hd / 16);
     const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
-    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT, CODES, RAGGED>), dim3(grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((kv_append_kernel<TIN, T, QUANT, CODES, RAGGED, PAGED>), dim3(grid), dim3(256), 0, st, p);
 }
 
 // The checks, the grid and the dtype dispatch both ABI entry points share (fn: the entry point's name for the messages).
 // The caller has checked what is its own: which pointers it requires, head_dim, nbits and the dtype pairs it admits.
-template <bool QUANT, bool CODES = false, bool RAGGED = false>
+template <bool QUANT, bool CODES = false, bool RAGGED = false, bool PAGED = false>
 int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* stream) {
     OQ_CHECK_ARG(!p.q || p.q_out, "%s: q without q_out", fn);
     OQ_CHECK_ARG(p.bs > 0 && p.Tq > 0 && p.nkv > 0 && p.nh >= 0 && (p.q || p.nh == 0), "%s: bad shape", fn);
     if constexpr (RAGGED) {
         OQ_CHECK_ARG(p.lens && (uintptr_t)p.lens % 4 == 0 && p.cap >= 0, "%s: lens (int32 [bs] on the device), cap >= 0", fn);
+        OQ_CHECK_ARG(PAGED == (p.pm.table != nullptr), "%s: page table", fn);
     } else {
         OQ_CHECK_ARG(!(p.kc || p.k_codes) || (p.past >= 0 && p.past + p.Tq <= p.cap), "%s: rows [%lld, %lld) exceed the capacity %lld", fn,
                      (long long)p.past, (long long)(p.past + p.Tq), (long long)p.cap);
@@ -204,11 +233,11 @@ int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* s
     for (const void* ptr : ptrs) OQ_CHECK_ARG(!ptr || oq_aligned16(ptr), "%s: tensors must be 16-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == OQ_F32 && in_dtype == OQ_F32) {
-        launch_append<float, float, QUANT, CODES, RAGGED>(p, st);
+        launch_append<float, float, QUANT, CODES, RAGGED, PAGED>(p, st);
     } else if (dtype == OQ_BF16 && in_dtype == OQ_BF16) {
-        launch_append<bf16_t, bf16_t, QUANT, CODES, RAGGED>(p, st);
+        launch_append<bf16_t, bf16_t, QUANT, CODES, RAGGED, PAGED>(p, st);
     } else if constexpr (QUANT) {
-        launch_append<float, bf16_t, true, CODES, RAGGED>(p, st);      // f32 -> bf16: the only other pair the quantising entry admits
+        launch_append<float, bf16_t, true, CODES, RAGGED, PAGED>(p, st);      // f32 -> bf16: the only other pair the quantising entry admits
     } else {
         oq_set_error("%s: dtype %d unsupported", fn, dtype);
         return OQ_E_UNSUPPORTED;
@@ -242,22 +271,28 @@ __device__ __forceinline__ float ld_mask(const void* m, int mdt, int64_t i) {
 
 // ---- where the cached rows come from: the kernel's K / V argument and its per-row loads ---------------------------------
 // A policy gives DPL (dims of a row one lane holds; HD / DPL lanes make a lane group), SCALED (a row carries a scale that
-// multiplies its score and its probability once per row), at(row0, d0) (the lane's view of one (b, kv head)), load(k, v, j)
-// of row j into Row registers, and Row::unpack / Row::scale.
+// multiplies its score and its probability once per row), at(b, kvh, nkv, cap, d0) (the lane's view of one (b, kv head)),
+// load(k, v, j) of that view's logical row j into Row registers -- false: the row has no storage and counts as invisible, which
+// only a paged cache can say -- and Row::unpack / Row::scale.
 template <typename T, int HD>
 struct FloatKV {                        // [bs, nkv, cap, HD] of T: 16-byte loads, 8 dims per lane
     static constexpr int DPL = 8;
     static constexpr bool SCALED = false;
+    static constexpr bool PAGED = false;
     const T *k, *v;
     struct Row {
         Raw8<T> r;
         __device__ __forceinline__ void unpack(float (&o)[8]) const { r.unpack(o); }
         __device__ __forceinline__ float scale() const { return 1.f; }
     };
-    __device__ __forceinline__ FloatKV at(int64_t row0, int d0) const { return {k + row0 * HD + d0, v + row0 * HD + d0}; }
-    __device__ __forceinline__ void load(Row& kr, Row& vr, int64_t j) const {
+    __device__ __forceinline__ FloatKV at(int64_t b, int kvh, int nkv, int64_t cap, int d0) const {
+        const int64_t row0 = (b * nkv + kvh) * cap;
+        return {k + row0 * HD + d0, v + row0 * HD + d0};
+    }
+    __device__ __forceinline__ bool load(Row& kr, Row& vr, int64_t j) const {
         kr.r.load(k + j * HD);
         vr.r.load(v + j * HD);
+        return true;
     }
 };
 
@@ -269,6 +304,7 @@ template <int HD, int DPL_>
 struct CodeKV {
     static constexpr int DPL = DPL_;
     static constexpr bool SCALED = true;
+    static constexpr bool PAGED = false;
     static constexpr int W = DPL / 8;
     const uint8_t *k, *v;
     const f32x2 *km, *vm;
@@ -298,14 +334,40 @@ struct CodeKV {
         }
         __device__ __forceinline__ float scale() const { return m[0]; }
     };
-    __device__ __forceinline__ CodeKV at(int64_t row0, int d0) const {
+    __device__ __forceinline__ CodeKV at(int64_t b, int kvh, int nkv, int64_t cap, int d0) const {
+        const int64_t row0 = (b * nkv + kvh) * cap;
         return {k + row0 * (HD / 2) + d0 / 2, v + row0 * (HD / 2) + d0 / 2, km + row0, vm + row0};
     }
-    __device__ __forceinline__ void load(Row& kr, Row& vr, int64_t j) const {
+    __device__ __forceinline__ bool load(Row& kr, Row& vr, int64_t j) const {
         kr.load(k + j * (HD / 2));
         vr.load(v + j * (HD / 2));
         kr.m = km[j];
         vr.m = vm[j];
+        return true;
+    }
+};
+
+// Either of the two over a page pool [num_pages, nkv, PS, ...]: the same rows, registers and arithmetic, found through the
+// page table.  at() moves the inner view to this kv head's rows of page 0 and the table to sequence b's row; load() reads
+// the lane group's own table entry (a vector load: the groups of a wave hold different rows j) and then the row, PS
+// contiguous rows per (page, kv head).  Callers keep j below the bound L <= max_pages * PS, so the entry exists.
+template <typename Inner>
+struct PagedKV {
+    static constexpr int DPL = Inner::DPL;
+    static constexpr bool SCALED = Inner::SCALED;
+    static constexpr bool PAGED = true;
+    using Row = typename Inner::Row;
+    Inner in;
+    PageMap pm;
+    int64_t page_rows;                  // rows from one page to the next: nkv << lg (set by at())
+    __device__ __forceinline__ PagedKV at(int64_t b, int kvh, int nkv, int64_t, int d0) const {
+        return {in.at(0, kvh, nkv, int64_t(1) << pm.lg, d0), {pm.table + b * pm.max_pages, pm.max_pages, pm.num_pages, pm.lg},
+                (int64_t)nkv << pm.lg};
+    }
+    __device__ __forceinline__ bool load(Row& kr, Row& vr, int64_t j) const {
+        const int64_t page = pm.table[j >> pm.lg];
+        if (page < 0 || page >= pm.num_pages) return false;
+        return in.load(kr, vr, page * page_rows + (j & ((int64_t(1) << pm.lg) - 1)));
     }
 };
 
@@ -318,6 +380,8 @@ struct CodeKV {
 // step, no mask tensor.  Rows >= lens[b] + Tq are never loaded; a split that starts there writes (m, l) = (-inf, 0) partials,
 // which the combine kernel weighs with 0.  lens[b] is the same for the whole workgroup, so the trip counts stay uniform.  With
 // every lens[b] == L - Tq and Tq == 1 the loops and the order of every sum are those of the plain instantiation.
+// A paged cache (PagedKV<>, RAGGED only) changes where load() finds row j and nothing else: the same loops and sums, hence the
+// bits of the contiguous cache holding the same rows, for every page size and page order.
 template <typename T, int HD, int QB, typename KV, bool RAGGED>
 __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, const KV kv_all, float* ws, int64_t Tq, int nh,
                                                                   int nkv, int64_t cap, int64_t L, float scale, const void* mask,
@@ -347,7 +411,7 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
         len = len < 0 ? 0 : (len > L - Tq ? L - Tq : len);
         if (j1 > len + Tq) j1 = len + Tq;
     }
-    const KV kv = kv_all.at((b * nkv + kvh) * cap, d0);
+    const KV kv = kv_all.at(b, kvh, nkv, cap, d0);
     float* wsb = ws + ((b * nkv + kvh) * ns + split) * R * (HD + 2);
     const float zs = scale * log2e;
 
@@ -381,8 +445,7 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t j = jb + u * G + grp;
-                ok[u] = j < j1;
-                if (ok[u]) kv.load(kr[u], vr[u], j);
+                ok[u] = j < j1 && kv.load(kr[u], vr[u], j);      // (a paged cache: and the row's page exists)
             }
             float z[U][QB];
 #pragma unroll
@@ -513,12 +576,16 @@ struct DecP {
     int64_t m_bs, m_ld;
     int ns;
     const int32_t* lens;                // per-sequence lengths (the RAGGED instantiations), or NULL
+    PageMap pm;                         // table != NULL: the buffers are page pools (PagedKV<>; lens required)
 };
 
 template <typename T, int HD, int QB, typename KV>
 void launch_decode(const DecP& p, const KV& kv, hipStream_t st) {
     const dim3 grid(p.ns, p.nkv, p.bs);
-    if (p.lens)
+    if constexpr (KV::PAGED)
+        hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV, true>), grid, dim3(DEC_THREADS), 0, st, (const T*)p.q, kv, p.ws, p.Tq,
+                           p.nh, p.nkv, p.cap, p.L, p.scale, nullptr, 0, 0, 0, p.ns, p.lens);
+    else if (p.lens)
         hipLaunchKernelGGL((attn_decode_kernel<T, HD, QB, KV, true>), grid, dim3(DEC_THREADS), 0, st, (const T*)p.q, kv, p.ws, p.Tq,
                            p.nh, p.nkv, p.cap, p.L, p.scale, nullptr, 0, 0, 0, p.ns, p.lens);
     else
@@ -529,9 +596,8 @@ void launch_decode(const DecP& p, const KV& kv, hipStream_t st) {
                        p.nkv, p.ns);
 }
 
-template <typename T, int HD>
-void launch_decode_float(int qb, const DecP& p, const void* kc, const void* vc, hipStream_t st) {
-    const FloatKV<T, HD> kv{(const T*)kc, (const T*)vc};
+template <typename T, int HD, typename KV>
+void launch_decode_qb(int qb, const DecP& p, const KV& kv, hipStream_t st) {
     switch (qb) {
         case 1: launch_decode<T, HD, 1>(p, kv, st); break;
         case 2: launch_decode<T, HD, 2>(p, kv, st); break;
@@ -540,35 +606,62 @@ void launch_decode_float(int qb, const DecP& p, const void* kc, const void* vc, 
     }
 }
 
+template <typename T, int HD>
+void launch_decode_float(int qb, const DecP& p, const void* kc, const void* vc, hipStream_t st) {
+    const FloatKV<T, HD> kv{(const T*)kc, (const T*)vc};
+    if (p.pm.table) return launch_decode_qb<T, HD>(qb, p, PagedKV<FloatKV<T, HD>>{kv, p.pm, 0}, st);
+    launch_decode_qb<T, HD>(qb, p, kv, st);
+}
+
 // One or two query rows per pass leave the registers for 16 dims per lane (8-byte loads); four or eight keep 8 dims.
 template <typename T, int HD>
 void launch_decode_codes(int qb, const DecP& p, const void* kc, const void* vc, const float* km, const float* vm, hipStream_t st) {
     const CodeKV<HD, 16> wide{(const uint8_t*)kc, (const uint8_t*)vc, (const f32x2*)km, (const f32x2*)vm};
     const CodeKV<HD, 8> narrow{wide.k, wide.v, wide.km, wide.vm};
-    switch (qb) {
-        case 1: launch_decode<T, HD, 1>(p, wide, st); break;
-        case 2: launch_decode<T, HD, 2>(p, wide, st); break;
-        case 4: launch_decode<T, HD, 4>(p, narrow, st); break;
-        default: launch_decode<T, HD, 8>(p, narrow, st); break;
+    if (p.pm.table) {
+        if (qb <= 2) launch_decode_qb<T, HD>(qb, p, PagedKV<CodeKV<HD, 16>>{wide, p.pm, 0}, st);
+        else launch_decode_qb<T, HD>(qb, p, PagedKV<CodeKV<HD, 8>>{narrow, p.pm, 0}, st);
+    } else if (qb <= 2) {
+        launch_decode_qb<T, HD>(qb, p, wide, st);
+    } else {
+        launch_decode_qb<T, HD>(qb, p, narrow, st);
     }
 }
 
 // ---- what an entry point and its ragged form share: the entry's own checks, then kv_append<> / the decode launch.  lens ==
 //      NULL: the uniform form (`past`, resp. L and the mask); else the ragged one (fn carries the entry point's name). ------------
+// The page map of a _paged entry point, checked (the table's values stay unread); *cap = the rows a sequence can address.
+const PageMap NO_PAGES{nullptr, 0, 0, 0};
+
+int page_map(const char* fn, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size, PageMap* pm, int64_t* cap) {
+    OQ_CHECK_ARG(page_size == 16 || page_size == 32 || page_size == 64 || page_size == 128, "%s: page_size %d (16, 32, 64 or 128)", fn,
+                 page_size);
+    OQ_CHECK_ARG(num_pages > 0 && max_pages > 0 && max_pages <= (INT64_MAX >> 8), "%s: num_pages %lld, max_pages %lld", fn,
+                 (long long)num_pages, (long long)max_pages);
+    OQ_CHECK_ARG(table && (uintptr_t)table % 4 == 0, "%s: table (int32 [bs, max_pages] on the device)", fn);
+    int lg = 4;
+    while ((1 << lg) < page_size) ++lg;
+    *pm = PageMap{table, max_pages, num_pages, lg};
+    *cap = max_pages * page_size;
+    return OQ_OK;
+}
+
 int append_plain(const char* fn, const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
                  int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past, const int32_t* lens,
-                 const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream) {
+                 const PageMap& pm, const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                 void* stream) {
     OQ_CHECK_ARG(k && v && k_cache && v_cache, "%s: null pointer", fn);
     OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "%s: head_dim %d must be a multiple of 16", fn, hd);
     const AppendP p{q, k, v, q_out, k_out, nullptr, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    0, 0.f, nullptr, nullptr, nullptr, nullptr, lens};
+                    0, 0.f, nullptr, nullptr, nullptr, nullptr, lens, pm};
+    if (pm.table) return kv_append<false, false, true, true>(fn, p, dtype, dtype, stream);
     return lens ? kv_append<false, false, true>(fn, p, dtype, dtype, stream) : kv_append<false>(fn, p, dtype, dtype, stream);
 }
 
 int append_quant(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
                  void* k_cache, void* v_cache, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
-                 const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
-                 int nbits, void* stream) {
+                 const int32_t* lens, const PageMap& pm, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                 int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(k && v, "%s: null k / v", fn);
     OQ_CHECK_ARG(!k_cache == !v_cache, "%s: the k and v caches go together", fn);
     OQ_CHECK_ARG(k_cache || (k_out && v_out), "%s: no destination for k / v (caches or k_out / v_out)", fn);
@@ -578,14 +671,15 @@ int append_quant(const char* fn, const void* q, const void* k, const void* v, in
     OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "%s: dtype %d (f32 or bf16)", fn, dtype);
     OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
     const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    nbits, 1.0f / (float)((1 << nbits) - 1), nullptr, nullptr, nullptr, nullptr, lens};
+                    nbits, 1.0f / (float)((1 << nbits) - 1), nullptr, nullptr, nullptr, nullptr, lens, pm};
+    if (pm.table) return kv_append<true, false, true, true>(fn, p, in_dtype, dtype, stream);
     return lens ? kv_append<true, false, true>(fn, p, in_dtype, dtype, stream) : kv_append<true>(fn, p, in_dtype, dtype, stream);
 }
 
 int append_codes(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
                  void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq, int nh, int nkv,
-                 int hd, int64_t cap, int64_t past, const int32_t* lens, const float* cos, const float* sin, int64_t P,
-                 const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
+                 int hd, int64_t cap, int64_t past, const int32_t* lens, const PageMap& pm, const float* cos, const float* sin,
+                 int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(k && v && k_codes && v_codes && k_meta && v_meta, "%s: null pointer", fn);
     OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
     OQ_CHECK_ARG(nbits == 4, "%s: %d-bit codes (4)", fn, nbits);
@@ -593,15 +687,17 @@ int append_codes(const char* fn, const void* q, const void* k, const void* v, in
     OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
     OQ_CHECK_ARG(!k_out == !v_out, "%s: k_out and v_out go together", fn);
     const AppendP p{q, k, v, q_out, k_out, v_out, nullptr, nullptr, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta, lens};
+                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta, lens, pm};
+    if (pm.table) return kv_append<true, true, true, true>(fn, p, in_dtype, dtype, stream);
     return lens ? kv_append<true, true, true>(fn, p, in_dtype, dtype, stream) : kv_append<true, true>(fn, p, in_dtype, dtype, stream);
 }
 
 // codes: k / v are the code buffers of a 4-bit cache and k_meta / v_meta its (scale, zero-point) pairs; else a float cache's
-// buffers (no meta).  ragged: lens is required and there is no mask; L is then the bound.
+// buffers (no meta).  ragged: lens is required and there is no mask; L is then the bound.  pm.table: the buffers are page
+// pools and cap = max_pages * page size (ragged only).
 int decode(const char* fn, bool codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
            int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, const int32_t* lens, bool ragged,
-           float scale, const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
+           const PageMap& pm, float scale, const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
            int64_t workspace_bytes, void* stream) {
     OQ_CHECK_ARG(q && k && v && o && workspace && (!codes || (k_meta && v_meta)) && (!ragged || lens), "%s: null pointer", fn);
     OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
@@ -618,7 +714,7 @@ int decode(const char* fn, bool codes, const void* q, const void* k, const void*
     OQ_CHECK_ARG(workspace_bytes >= need, "%s: workspace %lld < %lld bytes", fn, (long long)workspace_bytes, (long long)need);
     const int qb = dec_qb((int64_t)(nh / nkv) * Tq);
     const DecP p{q, o, (float*)workspace, bs, Tq, nh, nkv, cap, L, scale, mask, mask_dtype, mask_bstride, mask_ld, dec_splits(bs, nkv, L),
-                 lens};
+                 lens, pm};
     hipStream_t st = (hipStream_t)stream;
     if (dtype != OQ_F32 && dtype != OQ_BF16) {
         oq_set_error("%s: dtype %d unsupported", fn, dtype);
@@ -646,8 +742,8 @@ extern "C" int oq_kv_append(const void* q, const void* k, const void* v, void* q
                             int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past,
                             const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                             void* stream) {
-    return append_plain("oq_kv_append", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, past, nullptr, cos,
-                        sin, P, pos, pos_bstride, stream);
+    return append_plain("oq_kv_append", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, past, nullptr, NO_PAGES,
+                        cos, sin, P, pos, pos_bstride, stream);
 }
 
 extern "C" int oq_kv_append_ragged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache,
@@ -655,8 +751,8 @@ extern "C" int oq_kv_append_ragged(const void* q, const void* k, const void* v, 
                                    const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
                                    int64_t pos_bstride, void* stream) {
     OQ_CHECK_ARG(lens, "oq_kv_append_ragged: null lens");
-    return append_plain("oq_kv_append_ragged", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, 0, lens, cos,
-                        sin, P, pos, pos_bstride, stream);
+    return append_plain("oq_kv_append_ragged", q, k, v, q_out, k_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap, 0, lens, NO_PAGES,
+                        cos, sin, P, pos, pos_bstride, stream);
 }
 
 extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd) {
@@ -668,14 +764,14 @@ extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_
                               int nh, int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype,
                               int64_t mask_bstride, int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
     return decode("oq_attn_decode", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
-                  scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
+                  NO_PAGES, scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
 }
 
 extern "C" int oq_attn_decode_ragged(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs,
                                      int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound,
                                      float scale, void* workspace, int64_t workspace_bytes, void* stream) {
     return decode("oq_attn_decode_ragged", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
-                  true, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+                  true, NO_PAGES, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
@@ -683,7 +779,7 @@ extern "C" int oq_kv_append_quant(const void* q, const void* k, const void* v, i
                                   int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P, const int64_t* pos,
                                   int64_t pos_bstride, int nbits, void* stream) {
     return append_quant("oq_kv_append_quant", q, k, v, in_dtype, q_out, k_out, v_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd, cap,
-                        past, nullptr, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        past, nullptr, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_kv_append_quant_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
@@ -692,7 +788,7 @@ extern "C" int oq_kv_append_quant_ragged(const void* q, const void* k, const voi
                                          int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(lens, "oq_kv_append_quant_ragged: null lens");
     return append_quant("oq_kv_append_quant_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_cache, v_cache, dtype, bs, Tq, nh, nkv, hd,
-                        cap, 0, lens, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        cap, 0, lens, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
@@ -701,7 +797,7 @@ extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void
                                         const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                                         int nbits, void* stream) {
     return append_codes("oq_kv_append_quant_codes", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs,
-                        Tq, nh, nkv, hd, cap, past, nullptr, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        Tq, nh, nkv, hd, cap, past, nullptr, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_kv_append_quant_codes_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
@@ -711,7 +807,7 @@ extern "C" int oq_kv_append_quant_codes_ragged(const void* q, const void* k, con
                                                int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(lens, "oq_kv_append_quant_codes_ragged: null lens");
     return append_codes("oq_kv_append_quant_codes_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype,
-                        bs, Tq, nh, nkv, hd, cap, 0, lens, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        bs, Tq, nh, nkv, hd, cap, 0, lens, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
 }
 
 extern "C" int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
@@ -719,7 +815,7 @@ extern "C" int oq_attn_decode_codes(const void* q, const void* k_codes, const vo
                                     int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
                                     int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
     return decode("oq_attn_decode_codes", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
-                  scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
+                  NO_PAGES, scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
 }
 
 extern "C" int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
@@ -727,5 +823,62 @@ extern "C" int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, c
                                            int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                            int64_t workspace_bytes, void* stream) {
     return decode("oq_attn_decode_codes_ragged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
-                  lens, true, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+                  lens, true, NO_PAGES, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+}
+
+// ---- paged storage: the ragged entry points with (table, max_pages, num_pages, page_size) in the place of cap ------------------
+#define OQ_PAGE_MAP(fn)                                                                        \
+    PageMap pm;                                                                                \
+    int64_t cap;                                                                               \
+    OQ_CHECK_ARG(lens, fn ": null lens");                                                      \
+    if (const int rc = page_map(fn, table, max_pages, num_pages, page_size, &pm, &cap)) return rc
+
+extern "C" int oq_kv_append_paged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_pool, void* v_pool,
+                                  int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                                  int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, const float* cos,
+                                  const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream) {
+    OQ_PAGE_MAP("oq_kv_append_paged");
+    return append_plain("oq_kv_append_paged", q, k, v, q_out, k_out, k_pool, v_pool, dtype, bs, Tq, nh, nkv, hd, cap, 0, lens, pm, cos,
+                        sin, P, pos, pos_bstride, stream);
+}
+
+extern "C" int oq_kv_append_quant_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                        void* v_out, void* k_pool, void* v_pool, int dtype, int64_t bs, int64_t Tq, int nh, int nkv,
+                                        int hd, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                                        const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                                        int64_t pos_bstride, int nbits, void* stream) {
+    OQ_PAGE_MAP("oq_kv_append_quant_paged");
+    OQ_CHECK_ARG(k_pool && v_pool, "oq_kv_append_quant_paged: null pool");
+    return append_quant("oq_kv_append_quant_paged", q, k, v, in_dtype, q_out, k_out, v_out, k_pool, v_pool, dtype, bs, Tq, nh, nkv, hd,
+                        cap, 0, lens, pm, cos, sin, P, pos, pos_bstride, nbits, stream);
+}
+
+extern "C" int oq_kv_append_quant_codes_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                              void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype,
+                                              int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                                              int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens,
+                                              const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                                              int64_t pos_bstride, int nbits, void* stream) {
+    OQ_PAGE_MAP("oq_kv_append_quant_codes_paged");
+    return append_codes("oq_kv_append_quant_codes_paged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype,
+                        bs, Tq, nh, nkv, hd, cap, 0, lens, pm, cos, sin, P, pos, pos_bstride, nbits, stream);
+}
+
+extern "C" int oq_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, void* o, int dtype, int64_t bs, int64_t Tq,
+                                    int nh, int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages,
+                                    int page_size, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+    OQ_PAGE_MAP("oq_attn_decode_paged");
+    return decode("oq_attn_decode_paged", false, q, k_pool, v_pool, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+                  true, pm, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_decode_codes_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                          const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                          const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                                          const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    OQ_PAGE_MAP("oq_attn_decode_codes_paged");
+    return decode("oq_attn_decode_codes_paged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+                  lens, true, pm, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }

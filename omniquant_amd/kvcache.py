@@ -20,7 +20,13 @@ sequence b's valid rows are [0, lengths[b]), a step needs no padding mask and no
 launches depends on a length the host would have to read back.  `length` stays a host int, now an UPPER BOUND of
 lengths.max(): it sizes the buffers and the attention's split plan.  Rows of a sequence at or beyond its own length are
 scratch.  There is no common length, so the (k, v) tuple surface is refused; sequence(b) gives one sequence's rows.
+
+PagedKVCache (always ragged) drops the slab: rows live in pages of page_size rows per kv head, taken from one pool
+[num_pages, nkv, page_size, ...] per buffer by a PageAllocator and found through a per-sequence page table on the device
+(ops.*(..., page_table=)).  A sequence holds the pages its own rows need, a recycled slot returns its pages, and fork() lets
+two sequences share the full pages of a common prefix.
 """
+import heapq
 import operator
 
 import torch
@@ -224,3 +230,333 @@ class PackedKVCache:
         if self.ragged:
             c.lengths.copy_(self.lengths)
         return c
+
+
+class PageAllocator:
+    """Host bookkeeping of a pool of `num_pages` pages: a free list handed out in ascending page order and one reference count
+    per page (a page is free exactly when its count is 0).  Pure Python, no device; the same sequence of calls gives the same
+    page ids."""
+
+    def __init__(self, num_pages):
+        num_pages = operator.index(num_pages)
+        if num_pages <= 0:
+            raise OQError(f"PageAllocator: num_pages {num_pages}")
+        self.num_pages = num_pages
+        self._free = list(range(num_pages))         # a heap: ascending ids
+        self._refs = [0] * num_pages
+
+    @property
+    def n_free(self):
+        return len(self._free)
+
+    def refcount(self, page):
+        return self._refs[operator.index(page)]
+
+    def _held(self, what, pages):
+        pages = [operator.index(p) for p in pages]
+        for p in pages:
+            if not 0 <= p < self.num_pages or self._refs[p] <= 0:
+                raise OQError(f"PageAllocator.{what}: page {p} is not allocated")
+        return pages
+
+    def alloc(self, n):
+        """n fresh pages (reference count 1), the lowest free ids in ascending order; all or nothing."""
+        n = operator.index(n)
+        if n < 0 or n > len(self._free):
+            raise OQError(f"PageAllocator.alloc: {n} pages wanted, {len(self._free)} of {self.num_pages} free")
+        pages = [heapq.heappop(self._free) for _ in range(n)]
+        for p in pages:
+            self._refs[p] = 1
+        return pages
+
+    def retain(self, pages):
+        """One more reference to each of `pages` (allocated ones only)."""
+        pages = self._held("retain", pages)
+        for p in pages:
+            self._refs[p] += 1
+
+    def release(self, pages):
+        """Drop one reference to each of `pages`; a page whose count reaches 0 returns to the free list.  Releasing a page more
+        often than it is held is refused, and then nothing is released."""
+        pages = self._held("release", pages)
+        for p in set(pages):
+            if pages.count(p) > self._refs[p]:
+                raise OQError(f"PageAllocator.release: page {p} released {pages.count(p)} times, held {self._refs[p]} times")
+        for p in pages:
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                heapq.heappush(self._free, p)
+
+    def clone(self):
+        c = PageAllocator(self.num_pages)
+        c._free, c._refs = list(self._free), list(self._refs)
+        return c
+
+    def __repr__(self):
+        return f"PageAllocator({self.n_free} of {self.num_pages} pages free)"
+
+
+class PagedKVCache:
+    """One layer's paged, ragged KV cache.  Pools k / v [num_pages, nkv, page_size, hd] in `dtype` -- or, with code_bits=4,
+    k_codes / v_codes uint8 [num_pages, nkv, page_size, hd // 2] and k_meta / v_meta float32 [num_pages, nkv, page_size, 2] --
+    and page_table int32 [bs, max_pages] on the device: logical row j of sequence b lives in page page_table[b, j // page_size]
+    (entries of pages a sequence does not hold are -1, which the kernels neither store to nor load).  `lengths` (device) and
+    `length` (host upper bound) are a ragged PackedKVCache's; capacity = max_pages * page_size rows per sequence.
+
+    The host keeps a mirror of the table and, per sequence, an upper bound of its length: exact where lengths arrive as Python
+    ints (set_lengths, the block forwards' new_tokens), grown by the step's rows where they arrive as device tensors.  reserve()
+    allocates pages from the bounds and uploads the table only when it changed; no call of the step path reads the device.
+
+    Sharing invariant (fork): a page with more than one reference is never written.  Appends only write rows at or beyond a
+    sequence's own length; fork shares only pages that lie wholly below the forked length and copies the partial last page, and
+    set_lengths gives a sequence a private copy of a shared page before its length may point into it.  So every row at or
+    beyond a sequence's length lies in a page that sequence owns alone, and no copy-on-write is needed in the step."""
+
+    ragged = True
+    paged = True
+
+    def __init__(self, bs, nkv, hd, dtype, device, num_pages, page_size=16, max_pages=None, code_bits=None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise OQError(f"PagedKVCache needs a GPU device (got {device}); there is no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if dtype not in _DTYPES:
+            raise OQError(f"PagedKVCache: dtype {dtype} (the packed blocks compute in bfloat16 or float32)")
+        max_pages = num_pages if max_pages is None else max_pages
+        if min(int(bs), int(nkv), int(hd), int(num_pages), int(max_pages)) <= 0:
+            raise OQError(f"PagedKVCache: bs {bs}, nkv {nkv}, hd {hd}, num_pages {num_pages}, max_pages {max_pages}")
+        if page_size not in (16, 32, 64, 128):
+            raise OQError(f"PagedKVCache: page_size {page_size} (16, 32, 64 or 128)")
+        if int(hd) not in (64, 128):
+            raise OQError(f"PagedKVCache: head_dim {hd} (the decode kernels cover 64 and 128)")
+        if code_bits is not None and code_bits != 4:
+            raise OQError(f"PagedKVCache: code_bits {code_bits} (None: float rows, or 4)")
+        self.bs, self.nkv, self.hd, self.dtype, self.device = int(bs), int(nkv), int(hd), dtype, device
+        self.num_pages, self.page_size, self.max_pages, self.code_bits = int(num_pages), int(page_size), int(max_pages), code_bits
+        self.length = 0
+        self.lengths = torch.zeros(self.bs, dtype=torch.int32, device=device)
+        self.allocator = PageAllocator(self.num_pages)
+        self._pages = [[] for _ in range(self.bs)]          # host mirror of the table: the pages each sequence holds, in order
+        self._bound = [0] * self.bs                         # host upper bound of each length
+        self._exact = [True] * self.bs                      # ... which is the length itself (it came as a Python int)
+        self.page_table = torch.full((self.bs, self.max_pages), -1, dtype=torch.int32, device=device)
+        shape = (self.num_pages, self.nkv, self.page_size)
+        for name in self._buffers():
+            if code_bits is None:
+                t = torch.empty(shape + (self.hd,), dtype=dtype, device=device)
+            elif name.endswith("codes"):
+                t = torch.empty(shape + (self.hd // 2,), dtype=torch.uint8, device=device)
+            else:
+                t = torch.empty(shape + (2,), dtype=torch.float32, device=device)
+            setattr(self, name, t)
+
+    def _buffers(self):
+        """Names of the pool tensors of this kind (each [num_pages, nkv, page_size, ...])."""
+        return ("k", "v") if self.code_bits is None else ("k_codes", "v_codes", "k_meta", "v_meta")
+
+    @property
+    def capacity(self):
+        return self.max_pages * self.page_size
+
+    @property
+    def n_free(self):
+        return self.allocator.n_free
+
+    def nbytes(self):
+        """Bytes of device memory the pools and the page table hold."""
+        return sum(t.numel() * t.element_size() for t in [getattr(self, n) for n in self._buffers()] + [self.page_table])
+
+    def pages(self, b):
+        """The page ids sequence b holds, in row order (the host mirror of its table row)."""
+        return list(self._pages[operator.index(b)])
+
+    def _need(self, rows):
+        return -(-rows // self.page_size)
+
+    def _upload(self):
+        """The host mirror to the device: one non-blocking copy, ordered on the current stream behind the launches that read the
+        table it replaces."""
+        rows = [p + [-1] * (self.max_pages - len(p)) for p in self._pages]
+        self.page_table.copy_(torch.tensor(rows, dtype=torch.int32), non_blocking=True)
+
+    def _copy_page(self, src, dst):
+        for name in self._buffers():
+            t = getattr(self, name)
+            t[dst].copy_(t[src])
+
+    def reserve(self, n):
+        """Pages for n more rows of every sequence, counted from its host bound.  All or nothing: a sequence that would exceed
+        max_pages, or a pool without enough free pages, raises OQError before anything changes.  The table is uploaded only if
+        a page was added; a step inside the pages already held uploads nothing."""
+        n = int(n)
+        want = [max(self._need(bd + n) - len(p), 0) for bd, p in zip(self._bound, self._pages)]
+        for b, (w, p) in enumerate(zip(want, self._pages)):
+            if len(p) + w > self.max_pages or self.length + n > self.capacity:
+                raise OQError(f"{self!r}: {n} more rows take sequence {b} beyond max_pages = {self.max_pages} "
+                              f"({self.capacity} rows)")
+        if sum(want) > self.allocator.n_free:
+            raise OQError(f"{self!r}: {n} more rows per sequence need {sum(want)} pages, {self.allocator.n_free} are free")
+        if not any(want):
+            return
+        for w, p in zip(want, self._pages):
+            p.extend(self.allocator.alloc(w))
+        self._upload()
+
+    def advance(self, rows, counts=None, exact=True):
+        """Book a step of `rows` rows per sequence that the kernels have appended: the host bounds grow by `counts` (the valid
+        rows of each sequence as Python ints) or by `rows` -- exact=False: only an upper bound of what the sequences grew by,
+        their counts being a device tensor.  With counts, the pages that only the pad rows of a right-padded step made
+        reserve() take are returned to the pool.  The block forwards call this; `lengths` and `length` are theirs to update."""
+        if counts is None:
+            self._bound = [bd + int(rows) for bd in self._bound]
+            if not exact:
+                self._exact = [False] * self.bs
+            return
+        self._bound = [bd + int(c) for bd, c in zip(self._bound, counts)]
+        if self._trim():
+            self._upload()
+
+    def _trim(self):
+        """Release the pages beyond each sequence's bound; says whether the table changed."""
+        changed = False
+        for bd, p in zip(self._bound, self._pages):
+            keep = self._need(bd)
+            if len(p) > keep:
+                self.allocator.release(p[keep:])
+                del p[keep:]
+                changed = True
+        return changed
+
+    def set_lengths(self, lengths, bound=None):
+        """Set the per-sequence lengths, in the two forms of PackedKVCache.set_lengths.  Python ints: each sequence keeps the
+        pages its rows need and releases the rest -- set_lengths([n0, 0, n2]) returns all of slot 1's pages to the pool -- and
+        a sequence cut back into a page it shares first gets a private copy of that page (the sharing invariant).  A length
+        beyond the pages held takes fresh pages (their rows are scratch).  An int32 [bs] device tensor needs the host `bound`:
+        every sequence then holds pages for `bound` rows, none of them shared.  All or nothing; no device read."""
+        ps = self.page_size
+        if torch.is_tensor(lengths):
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (self.bs,) or lengths.device != self.device:
+                raise OQError(f"set_lengths: expected an int32 [{self.bs}] tensor on {self.device}, got {tuple(lengths.shape)} "
+                              f"{lengths.dtype} on {lengths.device}")
+            if bound is None:
+                raise OQError("set_lengths: a device tensor needs bound= (the host never reads the lengths back)")
+            top = int(bound)
+            bounds, exact, dev = [top] * self.bs, False, lengths
+        else:
+            seq = [operator.index(n) for n in lengths]
+            if len(seq) != self.bs or min(seq) < 0:
+                raise OQError(f"set_lengths: {seq} for a batch of {self.bs} (one length >= 0 per sequence)")
+            top = max(seq) if bound is None else int(bound)
+            if top < max(seq):
+                raise OQError(f"set_lengths: bound {top} below the longest sequence ({max(seq)})")
+            bounds, exact, dev = seq, True, torch.tensor(seq, dtype=torch.int32)
+        if not 0 <= top <= self.capacity:
+            raise OQError(f"set_lengths: bound {top} outside the capacity {self.capacity}")
+        # the plan: pages kept, pages whose private copy is needed (shared ones the sequence may now write), fresh pages
+        refs = self.allocator.refcount
+        keep = [min(self._need(bd), len(p)) if exact else len(p) for bd, p in zip(bounds, self._pages)]
+        fresh = [max(self._need(bd) - len(p), 0) for bd, p in zip(bounds, self._pages)]
+        copies = []
+        for b, (bd, p) in enumerate(zip(bounds, self._pages)):
+            first = bd // ps if exact else 0                # the first page the sequence may write from now on
+            copies += [(b, i) for i in range(first, keep[b]) if refs(p[i]) > 1]
+        dropped = [pg for b, p in enumerate(self._pages) for pg in p[keep[b]:]]
+        freed = sum(1 for pg in set(dropped) if dropped.count(pg) == refs(pg))
+        if len(copies) + sum(fresh) > self.allocator.n_free + freed:
+            raise OQError(f"{self!r}: set_lengths needs {len(copies) + sum(fresh)} pages, {self.allocator.n_free + freed} are free")
+        self.allocator.release(dropped)
+        for b, p in enumerate(self._pages):
+            del p[keep[b]:]
+        for b, i in copies:
+            (new,) = self.allocator.alloc(1)
+            self._copy_page(self._pages[b][i], new)
+            self.allocator.release([self._pages[b][i]])
+            self._pages[b][i] = new
+        for b, w in enumerate(fresh):
+            self._pages[b].extend(self.allocator.alloc(w))
+        if dropped or copies or any(fresh):
+            self._upload()
+        self.lengths.copy_(dev, non_blocking=True)
+        self._bound, self._exact, self.length = list(bounds), [exact] * self.bs, top
+
+    def fork(self, src, dst):
+        """Sequence dst, which must be empty, becomes a copy of sequence src: the pages that lie wholly below src's length are
+        shared by reference, a partial last page is copied into a fresh page (one device-side page copy per buffer), and dst's
+        length and bound become src's.  Both then append into pages of their own (the sharing invariant of the class).  src's
+        length must be known to the host exactly (set as Python ints / grown by new_tokens counts or whole steps from there)."""
+        src, dst = operator.index(src), operator.index(dst)
+        if not (0 <= src < self.bs and 0 <= dst < self.bs) or src == dst:
+            raise OQError(f"fork: sequences {src} -> {dst} of a batch of {self.bs}")
+        if self._bound[dst] != 0 or not self._exact[dst]:
+            raise OQError(f"fork: sequence {dst} is not empty (set_lengths with 0 for it first)")
+        if not self._exact[src]:
+            raise OQError(f"fork: the host holds only an upper bound of sequence {src}'s length (set_lengths with Python ints)")
+        n = self._bound[src]
+        full, part = n // self.page_size, 1 if n % self.page_size else 0
+        own = [pg for pg in self._pages[dst] if self.allocator.refcount(pg) == 1]
+        if part > self.allocator.n_free + len(own):
+            raise OQError(f"{self!r}: fork needs a page for the partial last page, none is free")
+        self.allocator.release(self._pages[dst])
+        shared = self._pages[src][:full]
+        self.allocator.retain(shared)
+        self._pages[dst] = list(shared)
+        if part:
+            (new,) = self.allocator.alloc(1)
+            self._copy_page(self._pages[src][full], new)
+            self._pages[dst].append(new)
+        self._upload()
+        self.lengths[dst:dst + 1].copy_(self.lengths[src:src + 1])
+        self._bound[dst] = n
+
+    def sequence(self, b):
+        """(k, v) of sequence b as [nkv, lengths[b], hd] copies in `dtype`, gathered from its pages (a code cache's are
+        dequantised by unpack_codes).  The one call that reads a length back from the device: for tests and debugging."""
+        b = operator.index(b)
+        if not 0 <= b < self.bs:
+            raise IndexError(f"sequence {b} of a batch of {self.bs}")
+        n = min(max(int(self.lengths[b]), 0), len(self._pages[b]) * self.page_size)
+        idx = torch.tensor(self._pages[b][:self._need(n)], dtype=torch.int64, device=self.device)
+
+        def rows(t):                                        # [pages, nkv, PS, x] -> [nkv, n, x]
+            return t[idx].transpose(0, 1).reshape(self.nkv, -1, t.shape[3])[:, :n]
+        if self.code_bits is None:
+            return rows(self.k).clone(), rows(self.v).clone()
+        return tuple(unpack_codes(rows(c), rows(m)).to(self.dtype)
+                     for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
+
+    # ---- the (k, v) tuple surface: refused, as for every ragged cache ------------------------------------------------------------
+    def _no_tuple(self, what):
+        raise OQError(f"{what}: a ragged cache has no common length, hence no [bs, nkv, length, hd] tensors; "
+                      "sequence(b) gives one sequence's rows")
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, i):
+        self._no_tuple("indexing")
+
+    def __iter__(self):
+        self._no_tuple("iteration")
+
+    def dequantize(self):
+        self._no_tuple("dequantize")
+
+    def to_tuple(self):
+        self._no_tuple("to_tuple")
+
+    def clone(self):
+        c = PagedKVCache(self.bs, self.nkv, self.hd, self.dtype, self.device, self.num_pages, self.page_size, self.max_pages,
+                         code_bits=self.code_bits)
+        for name in self._buffers():
+            getattr(c, name).copy_(getattr(self, name))
+        c.allocator = self.allocator.clone()
+        c._pages, c._bound, c._exact, c.length = [list(p) for p in self._pages], list(self._bound), list(self._exact), self.length
+        c.page_table.copy_(self.page_table)
+        c.lengths.copy_(self.lengths)
+        return c
+
+    def __repr__(self):
+        return (f"PagedKVCache(bs={self.bs}, nkv={self.nkv}, hd={self.hd}, dtype={self.dtype}, length={self.length}, paged: "
+                f"page_size={self.page_size}, {self.allocator.n_free} of {self.num_pages} pages free, max_pages={self.max_pages}"
+                + ("" if self.code_bits is None else f", code_bits={self.code_bits}") + ")")

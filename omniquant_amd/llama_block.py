@@ -349,7 +349,8 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual).  With a KV cache (past_key_value or use_cache;
         models/int_llama_layer.py:121-135,177,264-265) q / k are rotated at their positions and k / v appended to the cache in one
         launch, then attention runs over the whole cache.  Returns (hidden,) plus (present,) -- a PackedKVCache -- when use_cache.
-        A ragged PackedKVCache as past_key_value (one length per sequence, right-padded steps, new_tokens): _cached_attention."""
+        A ragged PackedKVCache as past_key_value (one length per sequence, right-padded steps, new_tokens): _cached_attention.
+        A kvcache.PagedKVCache (paged, ragged storage; the caller creates it) is taken in the same way."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if self.__dict__["_oq_packed"].get("act_quant"):
             return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens)

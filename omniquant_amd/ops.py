@@ -1635,6 +1635,40 @@ def _ragged_lengths(fn, lengths, bs, device, past=0):
     return lengths.contiguous()
 
 
+PAGE_SIZES = (16, 32, 64, 128)
+
+
+def _page_pool(fn, page_table, lengths, past, mask, bs, nkv, pools):
+    """Validate paged storage (kvcache.PagedKVCache): `pools` = ((tensor, last dim, dtype), ...) are page pools
+    [num_pages, nkv, PS, last dim] with PS in PAGE_SIZES, page_table an int32 [bs, max_pages] tensor on their device; paged
+    storage is ragged, so it needs lengths and takes neither a past nor a mask.  Host checks of shape, dtype and device only:
+    the values are never read.  Returns (contiguous table, max_pages, num_pages, PS)."""
+    if lengths is None:
+        raise C.OQError(f"{fn}: page_table needs lengths (paged storage is ragged: an int32 [{bs}] device tensor)")
+    if past:
+        raise C.OQError(f"{fn}: page_table excludes past = {past} (each sequence's past is lengths[b])")
+    if mask is not None:
+        raise C.OQError(f"{fn}: page_table excludes a mask (row t of sequence b attends rows <= lengths[b] + t)")
+    first = pools[0][0]
+    if first is None or not torch.is_tensor(first) or first.dim() != 4:
+        raise C.OQError(f"{fn}: page_table needs the page pools [num_pages, {nkv}, PS, ...] as the cache buffers")
+    num_pages, ps = first.shape[0], first.shape[2]
+    if ps not in PAGE_SIZES:
+        raise C.OQError(f"{fn}: pool {tuple(first.shape)} has a page size of {ps} rows (one of {PAGE_SIZES})")
+    for t, tail, dtype in pools:
+        if not torch.is_tensor(t) or tuple(t.shape) != (num_pages, nkv, ps, tail) or t.dtype != dtype or num_pages <= 0 \
+                or t.device != first.device:
+            what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+            raise C.OQError(f"{fn}: pool {what} (expected [num_pages > 0, {nkv}, {ps}, {tail}] {dtype} on {first.device})")
+    if not torch.is_tensor(page_table) or page_table.dtype != torch.int32 or page_table.dim() != 2 or page_table.shape[0] != bs \
+            or page_table.shape[1] <= 0:
+        what = f"{tuple(page_table.shape)} {page_table.dtype}" if torch.is_tensor(page_table) else type(page_table).__name__
+        raise C.OQError(f"{fn}: page_table must be an int32 [{bs}, max_pages] tensor, got {what}")
+    if page_table.device != first.device:
+        raise C.OQError(f"{fn}: page_table on {page_table.device}, the pool on {first.device}")
+    return page_table.contiguous(), page_table.shape[1], num_pages, ps
+
+
 def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, positions, lengths=None):
     """What kv_append and kv_append_quant validate alike: the caches (None: no cache) against k, the row range (lengths: the
     kernel guards it), q, the cos / sin tables and the positions.  Returns (cap, nh, P, pos_bstride, contiguous positions)."""
@@ -1666,25 +1700,38 @@ def _kv_append_args(fn, k, v, k_cache, v_cache, cache_dtype, past, q, cos, sin, 
     return cap, nh, P, pbs, positions
 
 
-def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None, lengths=None):
+def kv_append(k, v, k_cache, v_cache, past, q=None, q_out=None, k_out=None, cos=None, sin=None, positions=None, lengths=None,
+              page_table=None):
     """Append one step's k / v [bs, Tq, nkv, hd] to rows [past, past + Tq) of the [bs, nkv, cap, hd] caches in ONE launch
     (csrc/oq_decode.hip), rotating q (into q_out) and k with the cos / sin tables [P, hd] (rows = positions 0..P-1) gathered at
     `positions` (int64 [1 | bs, Tq]; None = past + t).  cos None: no rotation (OPT).  k_out: optional [bs, Tq, nkv, hd] copy
     of the rotated k (the prefill's attention reads it).
     lengths (ragged batches; past must be 0): int32 [bs] on the cache's device, one past per sequence, read by the kernel
     only (oq_kv_append_ragged): sequence b's row t goes to cache row lengths[b] + t and, with positions None, rotates at that
-    position.  A row outside [0, cap) is not stored to the cache (the kernel guards what the host cannot see)."""
+    position.  A row outside [0, cap) is not stored to the cache (the kernel guards what the host cannot see).
+    page_table (paged storage; needs lengths): int32 [bs, max_pages] on the device, and k_cache / v_cache are then the page
+    pools [num_pages, nkv, PS, hd] (oq_kv_append_paged): logical row lengths[b] + t lives in page page_table[b, row // PS].  A
+    row outside [0, max_pages * PS), or whose table entry is outside [0, num_pages), is not stored."""
     bs, Tq, nkv, hd = k.shape
+    pages = None
+    if page_table is not None:
+        pages = _page_pool("kv_append", page_table, lengths, past, None, bs, nkv, ((k_cache, hd, k.dtype), (v_cache, hd, k.dtype)))
     if lengths is not None:
         lengths = _ragged_lengths("kv_append", lengths, bs, k_cache.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype:
         raise C.OQError(f"kv_append: k {tuple(k.shape)} / v {tuple(v.shape)} differ")
-    cap, nh, P, pbs, positions = _kv_append_args("kv_append", k, v, k_cache, v_cache, k.dtype, past, q, cos, sin, positions, lengths)
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append", k, v, None if pages else k_cache, None if pages else v_cache, k.dtype,
+                                                 past, q, cos, sin, positions, lengths)
     if q is not None:
         q = q.contiguous()
         q_out = q if q_out is None else q_out
     k, v = k.contiguous(), v.contiguous()
     ragged = lengths is not None
+    if pages:
+        C.call("oq_kv_append_paged", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out), C.ptr(k_cache), C.ptr(v_cache), C.dt(k),
+               bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs,
+               C.stream())
+        return q_out
     C.call("oq_kv_append_ragged" if ragged else "oq_kv_append", C.ptr(q), C.ptr(k), C.ptr(v), C.ptr(q_out), C.ptr(k_out),
            C.ptr(k_cache), C.ptr(v_cache), C.dt(k), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos),
            C.fptr(sin), P, C.ptr(positions), pbs, C.stream())
@@ -1718,25 +1765,38 @@ def _code_buffers(fn, k_codes, v_codes, k_meta, v_meta, bs, nkv, hd):
 
 
 def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q=None, q_out=None, k_out=None, v_out=None,
-                    cos=None, sin=None, positions=None, lengths=None):
+                    cos=None, sin=None, positions=None, lengths=None, page_table=None):
     """kv_append_quant on the 4-bit grid with a code cache as the destination (csrc/oq_decode.hip, oq_kv_append_quant_codes):
     rows [past, past + Tq) of k_codes / v_codes (uint8 [bs, nkv, cap, hd // 2]) receive the quantiser's codes and k_meta /
     v_meta (float32 [bs, nkv, cap, 2]) its (scale, zero-point); (code - zp) * scale is, bit for bit, what kv_append_quant
     writes to a float32 cache.  q_out / k_out / v_out receive the fake-quant values in out_dtype as they do there.
-    lengths: as in kv_append (oq_kv_append_quant_codes_ragged)."""
+    lengths: as in kv_append (oq_kv_append_quant_codes_ragged).  page_table: as in kv_append, the four buffers being page pools
+    [num_pages, nkv, PS, hd // 2 | 2] (oq_kv_append_quant_codes_paged)."""
     bs, Tq, nkv, hd = k.shape
+    pages = None
+    if page_table is not None:
+        pages = _page_pool("kv_append_codes", page_table, lengths, past, None, bs, nkv,
+                           ((k_codes, hd // 2, torch.uint8), (v_codes, hd // 2, torch.uint8), (k_meta, 2, torch.float32),
+                            (v_meta, 2, torch.float32)))
+        if hd not in (64, 128):
+            raise C.OQError(f"kv_append_codes: head_dim {hd} (a code cache covers 64 and 128)")
     if lengths is not None:
         lengths = _ragged_lengths("kv_append_codes", lengths, bs, k_codes.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_codes: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
     _, nh, P, pbs, positions = _kv_append_args("kv_append_codes", k, v, None, None, out_dtype, past, q, cos, sin, positions)
-    cap = _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd)
+    cap = 0 if pages else _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd)
     ragged = lengths is not None
     if not ragged and (past < 0 or past + Tq > cap):
         raise C.OQError(f"kv_append_codes: rows [{past}, {past + Tq}) beyond the capacity {cap}")
     if (k_out is None) != (v_out is None):
         raise C.OQError("kv_append_codes: k_out and v_out go together")
     q, k, v = _kv_quant_outs("kv_append_codes", q, k, v, out_dtype, q_out, k_out, v_out)
+    if pages:
+        C.call("oq_kv_append_quant_codes_paged", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
+               C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype], bs, Tq, nh, nkv, hd, C.ptr(pages[0]),
+               *pages[1:], C.ptr(lengths), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4, C.stream())
+        return q_out
     C.call("oq_kv_append_quant_codes_ragged" if ragged else "oq_kv_append_quant_codes", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k),
            C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype],
            bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4,
@@ -1745,22 +1805,32 @@ def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q
 
 
 def kv_append_quant(k, v, nbits, out_dtype, k_cache=None, v_cache=None, past=0, q=None, q_out=None, k_out=None, v_out=None,
-                    cos=None, sin=None, positions=None, lengths=None):
+                    cos=None, sin=None, positions=None, lengths=None, page_table=None):
     """kv_append for the W4A4 packed blocks (csrc/oq_decode.hip, oq_kv_append_quant): q / k / v [bs, Tq, heads, hd] in float32
     or out_dtype are rotated (q, k; cos None: no rotation) exactly as kv_append rotates them, from fp32, then quantised per
     (token, head) over hd on the nbits asymmetric grid; the fake-quant values go, in out_dtype, to q_out, to cache rows
     [past, past + Tq) and to k_out / v_out.  The caches may be None (the no-cache forward: k_out and v_out then).
-    lengths: as in kv_append (oq_kv_append_quant_ragged; it needs the caches)."""
+    lengths: as in kv_append (oq_kv_append_quant_ragged; it needs the caches).  page_table: as in kv_append, k_cache / v_cache
+    being the page pools in out_dtype (oq_kv_append_quant_paged)."""
     bs, Tq, nkv, hd = k.shape
+    pages = None
+    if page_table is not None:
+        pages = _page_pool("kv_append_quant", page_table, lengths, past, None, bs, nkv,
+                           ((k_cache, hd, out_dtype), (v_cache, hd, out_dtype)))
     if lengths is not None:
         if k_cache is None:
             raise C.OQError("kv_append_quant: lengths without a cache")
         lengths = _ragged_lengths("kv_append_quant", lengths, bs, k_cache.device, past)
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_quant: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
-    cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, k_cache, v_cache, out_dtype, past, q, cos, sin, positions,
-                                                 lengths)
+    cap, nh, P, pbs, positions = _kv_append_args("kv_append_quant", k, v, None if pages else k_cache, None if pages else v_cache,
+                                                 out_dtype, past, q, cos, sin, positions, lengths)
     q, k, v = _kv_quant_outs("kv_append_quant", q, k, v, out_dtype, q_out, k_out, v_out)
+    if pages:
+        C.call("oq_kv_append_quant_paged", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
+               C.ptr(k_cache), C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths),
+               C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, int(nbits), C.stream())
+        return q_out
     ragged = lengths is not None
     C.call("oq_kv_append_quant_ragged" if ragged else "oq_kv_append_quant", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out),
            C.ptr(k_out), C.ptr(v_out), C.ptr(k_cache), C.ptr(v_cache), C._DT[out_dtype], bs, Tq, nh, nkv, hd, cap,
@@ -1806,17 +1876,30 @@ def _decode_mask(fn, mask, bs, Tq, L):
             mask.stride(2) if Tq > 1 else 0)
 
 
-def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=None, lengths=None):
+def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=None, lengths=None, page_table=None):
     """decode_attention over a 4-bit code cache (csrc/oq_decode.hip, oq_attn_decode_codes): `cache` is a PackedKVCache with
     code_bits 4 or the (k_codes, v_codes, k_meta, v_meta) buffers; K and V are dequantised in registers as (code - zp) * scale.
     Same scores, softmax, mask handling, split plan and reproducibility as decode_attention; q and o in the compute dtype.
-    lengths: as in decode_attention (oq_attn_decode_codes_ragged)."""
+    lengths: as in decode_attention (oq_attn_decode_codes_ragged).  page_table: as in decode_attention, `cache` being a
+    PagedKVCache's four page pools or the cache itself (oq_attn_decode_codes_paged)."""
     bs, Tq, nh, hd = q.shape
     bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
-    if len(bufs) != 4 or bufs[0].dim() != 4 or bufs[0].shape[0] != bs:
-        raise C.OQError(f"decode_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
-    nkv = bufs[0].shape[1]
-    cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd)
+    pages = None
+    if page_table is not None:
+        if len(bufs) != 4 or not torch.is_tensor(bufs[0]) or bufs[0].dim() != 4:
+            raise C.OQError("decode_attention_codes: page_table needs the (k_codes, v_codes, k_meta, v_meta) page pools")
+        if hd not in (64, 128):
+            raise C.OQError(f"decode_attention_codes: head_dim {hd} (a code cache covers 64 and 128)")
+        nkv = bufs[0].shape[1]
+        pages = _page_pool("decode_attention_codes", page_table, lengths, 0, mask, bs, nkv,
+                           ((bufs[0], hd // 2, torch.uint8), (bufs[1], hd // 2, torch.uint8), (bufs[2], 2, torch.float32),
+                            (bufs[3], 2, torch.float32)))
+        cap = pages[1] * pages[3]
+    else:
+        if len(bufs) != 4 or bufs[0].dim() != 4 or bufs[0].shape[0] != bs:
+            raise C.OQError(f"decode_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
+        nkv = bufs[0].shape[1]
+        cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd)
     if lengths is not None:
         lengths = _ragged_decode_args("decode_attention_codes", lengths, bs, bufs[0].device, mask, Tq, L, cap)
     if q.dtype not in (torch.float32, torch.bfloat16):
@@ -1827,6 +1910,11 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
     if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
     o = torch.empty_like(q) if out is None else out
+    if pages:
+        C.call("oq_attn_decode_codes_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+               C.dt(q), bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
+               workspace.numel() * workspace.element_size(), C.stream())
+        return o
     if lengths is not None:
         C.call("oq_attn_decode_codes_ragged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
                C.dt(q), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
@@ -1838,18 +1926,29 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
     return o
 
 
-def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None, lengths=None):
+def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspace=None, lengths=None, page_table=None):
     """o [bs, Tq, nh, hd] = softmax(max(scale * q k^T + mask, -FLT_MAX)) v over the first L rows of the [bs, nkv, cap, hd]
     caches (csrc/oq_decode.hip: split-L streaming, fp32 online softmax, one rounding).  mask: None or additive [bs | 1, 1, Tq, L]
     in float32 / float16 / bfloat16, read in place on the device (any batch / row stride; a batch of 1 is broadcast).
     lengths (ragged batches; mask must be None): int32 [bs] on the caches' device = the rows of each sequence BEFORE this step's
     append, read by the kernel only (oq_attn_decode_ragged).  L is then an upper bound of lengths[b] + Tq over the batch, L <= cap
-    (launches and workspace depend on it, never on the values); query row t of sequence b attends rows j <= lengths[b] + t."""
+    (launches and workspace depend on it, never on the values); query row t of sequence b attends rows j <= lengths[b] + t.
+    page_table (paged storage; needs lengths, no mask): int32 [bs, max_pages] on the device, and k_cache / v_cache are then the
+    page pools [num_pages, nkv, PS, hd] (oq_attn_decode_paged); L <= max_pages * PS.  A row whose table entry is outside
+    [0, num_pages) is invisible.  On the same rows, lengths and L the output is the contiguous ragged call's bit for bit."""
     bs, Tq, nh, hd = q.shape
-    if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
-            or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
-        raise C.OQError(f"decode_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
-    nkv, cap = k_cache.shape[1], k_cache.shape[2]
+    pages = None
+    if page_table is not None:
+        if not torch.is_tensor(k_cache) or k_cache.dim() != 4:
+            raise C.OQError("decode_attention: page_table needs the page pools [num_pages, nkv, PS, hd] as k_cache / v_cache")
+        nkv = k_cache.shape[1]
+        pages = _page_pool("decode_attention", page_table, lengths, 0, mask, bs, nkv, ((k_cache, hd, q.dtype), (v_cache, hd, q.dtype)))
+        cap = pages[1] * pages[3]
+    else:
+        if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
+                or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+            raise C.OQError(f"decode_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
+        nkv, cap = k_cache.shape[1], k_cache.shape[2]
     if lengths is not None:
         lengths = _ragged_decode_args("decode_attention", lengths, bs, k_cache.device, mask, Tq, L, cap)
     q = q.contiguous()
@@ -1858,6 +1957,11 @@ def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspa
     if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
     o = torch.empty_like(q) if out is None else out
+    if pages:
+        C.call("oq_attn_decode_paged", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd,
+               C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
+               workspace.numel() * workspace.element_size(), C.stream())
+        return o
     if lengths is not None:
         C.call("oq_attn_decode_ragged", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd, cap,
                C.ptr(lengths), int(L), float(scale), C.ptr(workspace), workspace.numel() * workspace.element_size(), C.stream())

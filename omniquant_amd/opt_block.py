@@ -142,7 +142,8 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
                         new_tokens=None):
         """Real-quant inference (realquant.pack_block): the same block with LayerNorm, biased PackedLinears and ReLU.
         new_tokens (the keyword of forward's **kwargs): the valid rows per sequence of a right-padded step on a ragged
-        PackedKVCache (_cached_attention)."""
+        PackedKVCache (_cached_attention); a kvcache.PagedKVCache (paged, ragged storage; the caller creates it) is taken in
+        the same way."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if layer_head_mask is not None:
             raise NotImplementedError("the packed inference path runs without head masks")

@@ -24,8 +24,16 @@
    `--rounds` times.  A row reports median / min / max per kernel, the bytes each must read, the run-to-run spread (max -
    min over the median) of both bf16 kernels and the ratios of the medians.
 
+5. `--paged`: instead of 1 and 2, paged against ragged contiguous storage at the same lengths: a batch of 8 sequences of
+   mixed lengths (geometric, L / 64 ... L) at the 7B shape, Tq = 1, bounds L = 8192 and 32768, on a bf16 cache and on a 4-bit
+   code cache.  oq_attn_decode_paged / oq_attn_decode_codes_paged with page sizes 16 and 128, on pools that hold exactly the
+   pages the lengths need, in a random page order, against oq_attn_decode_ragged / oq_attn_decode_codes_ragged on
+   [bs, nkv, L, hd] slabs.  Cold cache sets, the three graphs of a row replayed alternately `--rounds` times; a row reports
+   median / min / max per kernel, the contiguous kernel's run-to-run spread (max - min over its median) and the ratios of
+   the medians.  Then the three appends' paged forms next to their ragged forms at Tq = 1 (bound 8192).
+
 usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
-                                         [--codes | --ragged [--rounds 7]]
+                                         [--codes | --ragged | --paged [--rounds 7]]
 """
 import argparse
 import json
@@ -238,6 +246,105 @@ def ragged_rows(reps, rounds, dev):
     return [r]
 
 
+def paged_rows(reps, rounds, quick, dev):
+    name, nh, nkv, hd = SHAPES[0]
+    bs, scale = 8, hd ** -0.5
+    rows = []
+    q = torch.randn(bs, 1, nh, hd, device=dev).bfloat16()
+    o = torch.empty_like(q)
+
+    def tensors(kind, lead):
+        """K and V of a cache kind with leading dims `lead` + (rows,): (k, v) bf16, or (k_codes, v_codes, k_meta, v_meta)."""
+        if kind == "bf16":
+            return tuple(torch.randn(*lead, hd, device=dev).bfloat16() for _ in range(2))
+        out = [torch.randint(0, 256, (*lead, hd // 2), dtype=torch.uint8, device=dev) for _ in range(2)]
+        for _ in range(2):
+            m = torch.empty(*lead, 2, device=dev)
+            m[..., 0] = torch.rand(*lead, device=dev) * 0.1 + 0.3
+            m[..., 1] = torch.randint(5, 11, tuple(lead), device=dev).float()
+            out.append(m)
+        return tuple(out)
+
+    def attend(kind, s, L, lens, table=None):
+        if kind == "bf16":
+            return lambda: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws, lengths=lens, page_table=table)
+        return lambda: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws, lengths=lens, page_table=table)
+
+    def table_of(lengths, ps, L, seed):
+        """A pool of exactly the pages the lengths need, handed out in a random order; unused entries -1."""
+        need = [-(-n // ps) for n in lengths]
+        perm = torch.randperm(sum(need), generator=torch.Generator().manual_seed(seed)).tolist()
+        t = torch.full((bs, L // ps), -1, dtype=torch.int32)
+        at = 0
+        for b, n in enumerate(need):
+            t[b, :n] = torch.tensor(perm[at:at + n], dtype=torch.int32)
+            at += n
+        return t.to(dev), sum(need)
+
+    for L in ((8192,) if quick else (8192, 32768)):
+        lengths = [n * (L // 8192) for n in RAGGED_LENGTHS]
+        lens = torch.tensor([n - 1 for n in lengths], dtype=torch.int32, device=dev)
+        ws = torch.empty(C.size_call("oq_attn_decode_workspace", bs, nh, nkv, 1, L, hd), dtype=torch.uint8, device=dev)
+        for kind, row_bytes in (("bf16", 2 * hd), ("codes", hd // 2 + 8)):
+            need = 2 * nkv * sum(lengths) * row_bytes
+            nsets = max(2, -(-COLD_BYTES // need))
+            launches = [[attend(kind, tensors(kind, (bs, nkv, L)), L, lens) for _ in range(nsets)]]
+            pools = {}
+            for ps in (16, 128):
+                fns = []
+                for i in range(nsets):
+                    table, num_pages = table_of(lengths, ps, L, 100 * ps + i)
+                    fns.append(attend(kind, tensors(kind, (num_pages, nkv, ps)), L, lens, table))
+                pools[ps] = num_pages
+                launches.append(fns)
+            us, med = interleaved(launches, reps, rounds)
+            r = dict(what="attention", shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, lengths=lengths, L_bound=L, Tq=1, cache=kind,
+                     sets=nsets, rounds=rounds, bytes=need, slab_rows=bs * L, pool_rows_ps16=pools[16] * 16,
+                     pool_rows_ps128=pools[128] * 128)
+            for i, k in enumerate(("contiguous", "paged16", "paged128")):
+                r.update({k + "_us": med[i], k + "_us_min": min(us[i]), k + "_us_max": max(us[i]), k + "_GBps": need / med[i] / 1e3})
+            r.update(contiguous_spread=(max(us[0]) - min(us[0])) / med[0], paged16_over_contiguous=med[1] / med[0],
+                     paged128_over_contiguous=med[2] / med[0])
+            rows.append(r)
+            print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+            del launches, fns
+            torch.cuda.empty_cache()
+    # the appends at Tq = 1 (bound 8192): one row per sequence and kv head, the launch dominates
+    L = 8192
+    lengths = RAGGED_LENGTHS
+    lens = torch.tensor([n - 1 for n in lengths], dtype=torch.int32, device=dev)
+    cos, sin = torch.randn(L, hd, device=dev), torch.randn(L, hd, device=dev)
+    k32, v32 = (torch.randn(bs, 1, nkv, hd, device=dev) for _ in range(2))
+    q32 = torch.randn(bs, 1, nh, hd, device=dev)
+    qo = torch.empty_like(q)
+    ko, vo = (torch.empty(bs, 1, nkv, hd, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    kb, vb = k32.bfloat16(), v32.bfloat16()
+    for kind in ("plain", "quant", "codes"):
+        def append(bufs, table=None, kind=kind):
+            kw = dict(q_out=qo, cos=cos, sin=sin, lengths=lens, page_table=table)
+            if kind == "plain":
+                return lambda: ops.kv_append(kb, vb, bufs[0], bufs[1], 0, q=q, **kw)
+            if kind == "quant":
+                return lambda: ops.kv_append_quant(k32, v32, 4, torch.bfloat16, k_cache=bufs[0], v_cache=bufs[1], q=q32, k_out=ko,
+                                                   v_out=vo, **kw)
+            return lambda: ops.kv_append_codes(k32, v32, torch.bfloat16, *bufs, q=q32, k_out=ko, v_out=vo, **kw)
+
+        store = "codes" if kind == "codes" else "bf16"
+        launches = [[append(tensors(store, (bs, nkv, L)))]]
+        for ps in (16, 128):
+            table, num_pages = table_of(lengths, ps, L, ps)
+            launches.append([append(tensors(store, (num_pages, nkv, ps)), table)])
+        us, med = interleaved(launches, reps * 10, rounds)
+        r = dict(what="append " + kind, shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, Tq=1, L_bound=L, rounds=rounds)
+        for i, k in enumerate(("contiguous", "paged16", "paged128")):
+            r.update({k + "_us": med[i], k + "_us_min": min(us[i]), k + "_us_max": max(us[i])})
+        r.update(contiguous_spread=(max(us[0]) - min(us[0])) / med[0], paged16_over_contiguous=med[1] / med[0],
+                 paged128_over_contiguous=med[2] / med[0])
+        rows.append(r)
+        print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+    return rows
+
+
 def packed_7b_block(dev, L_cap):
     """A LLaMA-7B block with random W4 g128 AutoGPTQ buffers (the decode step's cost does not depend on their values)."""
     from omniquant_amd.calibrate import decoder_layer_class, default_args
@@ -337,7 +444,8 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--codes", action="store_true", help="the code-cache kernel interleaved with the bf16-cache kernel")
     ap.add_argument("--ragged", action="store_true", help="ragged-batch kernels interleaved with the padded, masked ones")
-    ap.add_argument("--rounds", type=int, default=7, help="--codes / --ragged: alternating replays of the graphs")
+    ap.add_argument("--paged", action="store_true", help="paged kernels interleaved with the ragged contiguous ones")
+    ap.add_argument("--rounds", type=int, default=7, help="--codes / --ragged / --paged: alternating replays of the graphs")
     a = ap.parse_args()
     dev = "cuda:0"
     if not torch.cuda.is_available():
@@ -346,7 +454,9 @@ def main():
     if a.step_only:
         block_step(dev, a.reps, steps_only=a.steps)
         return
-    if a.ragged:
+    if a.paged:
+        rows = paged_rows(a.reps, a.rounds, a.quick, dev)
+    elif a.ragged:
         rows = ragged_rows(a.reps, a.rounds, dev)
     elif a.codes:
         rows = codes_rows(a.reps, a.rounds, a.quick, dev)
