@@ -449,6 +449,35 @@ int oq_attn_decode_codes_paged(const void* q, const void* k_codes, const void* v
                                int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
                                float scale, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*   Chunked prefill ("extend": many query rows over a cache that has a past; csrc/oq_extend.hip): the values of the four
+ *      oq_attn_decode_*_ragged / _paged entry points, with their argument lists, computed on the bf16 MFMA: query row t of
+ *      sequence b attends cache rows j <= lens[b] + t, lens[b] < 0 counts as 0 and lens[b] > L_bound - Tq as L_bound - Tq, rows
+ *      >= lens[b] + Tq and rows whose table entry lies outside [0, num_pages) are never loaded (they count as masked), and the
+ *      launch grid, split plan and workspace (oq_attn_extend_workspace; 0 bytes when the plan has one split) depend on the
+ *      shape and L_bound only.  A query tile holds rows r = t * (nh / nkv) + i of one kv head, so the query heads of a GQA
+ *      group share each 64-row K/V tile; scores, maximum, row sum and accumulator are fp32, the probabilities (code caches:
+ *      probability * row scale of V) meet V as bf16.  Code rows enter the product as code - zero_point (exact in bf16 up to
+ *      256 in magnitude), the row scales multiply score and probability once per row.  Partials use the decode workspace
+ *      layout and the decode combine kernel.  Bit-identical run to run; the paged forms give the slab forms' bits on the same
+ *      rows for every page size and page order.
+ *      dtype OQ_BF16 (q, o and a float cache) and head_dim 64 / 128 only: oq_attn_extend_supported() says whether a problem
+ *      qualifies, everything else returns OQ_E_UNSUPPORTED and stays with oq_attn_decode_*.  There is no mask argument. */
+int64_t oq_attn_extend_supported(int dtype, int64_t Tq, int hd);
+int64_t oq_attn_extend_workspace(int64_t bs, int nh, int nkv, int64_t Tq, int64_t L, int hd);
+int oq_attn_extend(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
+                   int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int oq_attn_extend_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta, void* o,
+                         int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens,
+                         int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_attn_extend_paged(const void* q, const void* k_pool, const void* v_pool, void* o, int dtype, int64_t bs, int64_t Tq, int nh,
+                         int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                         const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_attn_extend_codes_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                               void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                               int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
+                               float scale, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,

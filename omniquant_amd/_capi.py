@@ -102,6 +102,13 @@ SIGNATURES = {
                              _i64, _vp],
     "oq_attn_decode_codes_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
                                    _i64, _f32, _vp, _i64, _vp],
+    # chunked prefill over the cache: the argument lists of the decode forms above
+    "oq_attn_extend": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
+    "oq_attn_extend_codes": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
+    "oq_attn_extend_paged": [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _f32, _vp,
+                             _i64, _vp],
+    "oq_attn_extend_codes_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
+                                   _i64, _f32, _vp, _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,
@@ -143,7 +150,8 @@ SIZE_FUNCS = {"oq_fakequant_bwd_workspace": [_i64, _i64], "oq_norm_bwd_workspace
               "oq_norm_quant_supported": [_i32, _i64], "oq_norm_quant_bwd_workspace": [_i64, _i64],
               "oq_fakequant_codes_supported": [_i64, _i64, _i32, _i32], "oq_packed_gemv_workspace": [_i64, _i64, _i64, _i32],
               "oq_packed_gemv_a4_workspace": [_i64, _i64, _i64],
-              "oq_attn_decode_workspace": [_i64, _i32, _i32, _i64, _i64, _i32]}
+              "oq_attn_decode_workspace": [_i64, _i32, _i32, _i64, _i64, _i32],
+              "oq_attn_extend_workspace": [_i64, _i32, _i32, _i64, _i64, _i32], "oq_attn_extend_supported": [_i32, _i64, _i32]}
 
 _lib = None
 

@@ -16,6 +16,11 @@ from .linear import QuantLinear
 from .matmul import QuantMatMul
 
 
+#: Steps of at least this many query rows over a ragged / paged bfloat16 cache with a past run the MFMA chunked-prefill
+#: attention (oq_attn_extend*); shorter ones stay on the decode kernel.  Never below 16 (the measurement).
+EXTEND_MIN_TQ = 16
+
+
 class QuantBlockMixin:
     #: activation / temp-weight dtype of the HIP path: torch.bfloat16 (MFMA bf16) or torch.float32 (exact)
     compute_dtype = torch.bfloat16
@@ -154,6 +159,9 @@ class QuantBlockMixin:
         keeps right padding away from the valid rows; the append goes at lengths = 0).  With a past the mask must be None
         (row t of sequence b attends rows <= lengths[b] + t) and positions None leaves them to the kernel (lengths[b] + t).
         A decode step on a ragged cache performs no device-to-host read and builds no mask or position tensor.
+        A step of Tq >= EXTEND_MIN_TQ rows over a ragged bfloat16 cache with a past (a prompt chunk, a forked prefix's suffix, a
+        new turn, draft tokens) runs ops.extend_attention / extend_attention_codes instead of the decode kernel (_extend_step):
+        the same lengths, L and pad-row contract, the same absence of host reads.
         A paged cache (cache.paged, always ragged; kvcache.PagedKVCache): the same ops calls on its page pools with
         page_table=cache.page_table; reserve() gives every sequence the pages the step's rows need (uploading the table only
         if one was added) and advance() books the step in the cache's host bounds.  Nothing else about the step changes."""
@@ -196,6 +204,11 @@ class QuantBlockMixin:
             if mask is not None and mask.shape[0] != bsz:
                 mask = mask.expand(bsz, 1, Tq, L)
             attn = self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
+        elif self._extend_step(cache, qr, Tq):
+            if cache.code_bits is not None:
+                attn = ops.extend_attention_codes(qr, cache, L, scale, lens, **paged)
+            else:
+                attn = ops.extend_attention(qr, cache.k, cache.v, L, scale, lens, **paged)
         elif cache.code_bits is not None:
             attn = ops.decode_attention_codes(qr, cache, L, scale, attention_mask, lengths=lens, **paged)
         else:
@@ -208,6 +221,15 @@ class QuantBlockMixin:
             if paged:
                 cache.advance(Tq, host_counts, exact=counts is None or host_counts is not None)
         return attn
+
+    @staticmethod
+    def _extend_step(cache, q, Tq):
+        """Whether a step with a past goes to ops.extend_attention*: a ragged (or paged) bfloat16 cache and Tq >= EXTEND_MIN_TQ.
+        OQ_NO_EXTEND=1 is the A/B switch: every step with a past then stays on the decode kernel."""
+        from . import ops
+        if not cache.ragged or Tq < EXTEND_MIN_TQ or os.environ.get("OQ_NO_EXTEND"):
+            return False
+        return cache.dtype == torch.bfloat16 and ops.extend_attention_supported(q.dtype, Tq, q.shape[3])
 
     @staticmethod
     def _packed_attention(q, k, v, attention_mask, scale):

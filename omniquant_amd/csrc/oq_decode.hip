@@ -13,18 +13,9 @@
 // problem the bits do not change from launch to launch, nor with the cache capacity.
 #include "oq_common.h"
 #include "oq_quant_dev.h"
+#include "oq_kv_dev.h"
 
 namespace {
-
-// Paged storage: the rows of a cache live in pages of PS = 1 << lg rows per kv head, pool buffers [num_pages, nkv, PS, ...],
-// and logical row j of sequence b is row j & (PS - 1) of page table[b * max_pages + (j >> lg)].  table == NULL: the contiguous
-// [bs, nkv, cap, ...] slab.  The host never reads the table, so the kernels guard its entries: a row whose entry lies outside
-// [0, num_pages) is neither stored (append) nor loaded (attention, where it counts as invisible).
-struct PageMap {
-    const int32_t* table;               // int32 [bs, max_pages] on the device
-    int64_t max_pages, num_pages;
-    int lg;
-};
 
 // ---- KV append: q [bs,Tq,nh,hd], k / v [bs,Tq,nkv,hd] -> rotated q (q_out), rotated k (cache rows past.., and k_out),
 //      plain v (cache, and v_out).  One work item = 8 elements of a head's first half and the 8 partners of its second half.
@@ -248,19 +239,6 @@ int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* s
 
 // ---- decode attention ----------------------------------------------------------------------------------------------------
 constexpr int DEC_THREADS = 256;
-constexpr int DEC_TARGET_WG = 1024;     // 4 workgroups of 4 waves per CU
-constexpr int DEC_MAX_SPLIT = 64;
-constexpr int DEC_MIN_KEYS = 128;       // a split covers at least this many cached rows (L <= 128: one split)
-
-// The split count depends on the problem shape only (never on cap or on the data): results are reproducible bit for bit.
-inline int dec_splits(int64_t bs, int64_t nkv, int64_t L) {
-    int64_t ns = (DEC_TARGET_WG + bs * nkv - 1) / (bs * nkv);
-    if (ns > DEC_MAX_SPLIT) ns = DEC_MAX_SPLIT;
-    const int64_t by_len = (L + DEC_MIN_KEYS - 1) / DEC_MIN_KEYS;
-    if (ns > by_len) ns = by_len;
-    return ns < 1 ? 1 : (int)ns;
-}
-
 inline int dec_qb(int64_t R) { return R >= 8 ? 8 : (R >= 3 ? 4 : (R == 2 ? 2 : 1)); }
 
 __device__ __forceinline__ float ld_mask(const void* m, int mdt, int64_t i) {
@@ -539,30 +517,6 @@ __global__ void __launch_bounds__(DEC_THREADS) attn_decode_kernel(const T* q, co
     }
 }
 
-// Combine kernel: one workgroup of HD threads per (b, kv head, r); splits merged in split order, one rounding to T.
-template <typename T, int HD>
-__global__ void __launch_bounds__(HD) attn_decode_combine_kernel(const float* ws, T* o, int64_t Tq, int nh, int nkv, int ns) {
-    const int rep = nh / nkv;
-    const int64_t R = (int64_t)rep * Tq;
-    const int64_t row = blockIdx.x;
-    const int64_t r = row % R, bk = row / R;
-    const int64_t kvh = bk % nkv, b = bk / nkv;
-    const int tid = threadIdx.x;
-    const float* w = ws + (bk * ns * R + r) * (HD + 2);
-    const int64_t st = R * (HD + 2);
-    float M = -INFINITY;
-    for (int s = 0; s < ns; ++s) M = fmaxf(M, w[s * st]);
-    float l = 0.f, a = 0.f;
-    for (int s = 0; s < ns; ++s) {
-        const float ms = w[s * st];
-        const float f = ms == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(ms - M);
-        l += f * w[s * st + 1];
-        a += f * w[s * st + 2 + tid];
-    }
-    const int64_t t = r / rep;
-    st1(o + ((b * Tq + t) * nh + kvh * rep + (r % rep)) * HD + tid, a / l);
-}
-
 struct DecP {
     const void* q;
     void* o;
@@ -630,22 +584,6 @@ void launch_decode_codes(int qb, const DecP& p, const void* kc, const void* vc, 
 
 // ---- what an entry point and its ragged form share: the entry's own checks, then kv_append<> / the decode launch.  lens ==
 //      NULL: the uniform form (`past`, resp. L and the mask); else the ragged one (fn carries the entry point's name). ------------
-// The page map of a _paged entry point, checked (the table's values stay unread); *cap = the rows a sequence can address.
-const PageMap NO_PAGES{nullptr, 0, 0, 0};
-
-int page_map(const char* fn, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size, PageMap* pm, int64_t* cap) {
-    OQ_CHECK_ARG(page_size == 16 || page_size == 32 || page_size == 64 || page_size == 128, "%s: page_size %d (16, 32, 64 or 128)", fn,
-                 page_size);
-    OQ_CHECK_ARG(num_pages > 0 && max_pages > 0 && max_pages <= (INT64_MAX >> 8), "%s: num_pages %lld, max_pages %lld", fn,
-                 (long long)num_pages, (long long)max_pages);
-    OQ_CHECK_ARG(table && (uintptr_t)table % 4 == 0, "%s: table (int32 [bs, max_pages] on the device)", fn);
-    int lg = 4;
-    while ((1 << lg) < page_size) ++lg;
-    *pm = PageMap{table, max_pages, num_pages, lg};
-    *cap = max_pages * page_size;
-    return OQ_OK;
-}
-
 int append_plain(const char* fn, const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_cache, void* v_cache,
                  int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t past, const int32_t* lens,
                  const PageMap& pm, const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
@@ -827,12 +765,6 @@ extern "C" int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, c
 }
 
 // ---- paged storage: the ragged entry points with (table, max_pages, num_pages, page_size) in the place of cap ------------------
-#define OQ_PAGE_MAP(fn)                                                                        \
-    PageMap pm;                                                                                \
-    int64_t cap;                                                                               \
-    OQ_CHECK_ARG(lens, fn ": null lens");                                                      \
-    if (const int rc = page_map(fn, table, max_pages, num_pages, page_size, &pm, &cap)) return rc
-
 extern "C" int oq_kv_append_paged(const void* q, const void* k, const void* v, void* q_out, void* k_out, void* k_pool, void* v_pool,
                                   int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
                                   int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, const float* cos,

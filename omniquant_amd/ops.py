@@ -1971,6 +1971,92 @@ def decode_attention(q, k_cache, v_cache, L, scale, mask=None, out=None, workspa
     return o
 
 
+def extend_attention_supported(dtype, Tq, hd):
+    """Whether extend_attention / extend_attention_codes cover a step (oq_attn_extend_supported): bfloat16, head_dim 64 or 128."""
+    return dtype in C._DT and bool(C.size_call("oq_attn_extend_supported", C._DT[dtype], int(Tq), int(hd)))
+
+
+def _extend_args(fn, q, lengths, bs, device, Tq, L, cap, nh, nkv, out, workspace):
+    """What the two chunked-prefill attentions validate alike once the cache buffers are checked; returns (contiguous q, lengths,
+    o, workspace, its size in bytes)."""
+    if lengths is None:
+        raise C.OQError(f"{fn}: lengths is required (an int32 [{bs}] device tensor: the rows of each sequence before this step)")
+    lengths = _ragged_decode_args(fn, lengths, bs, device, None, Tq, L, cap)
+    if not extend_attention_supported(q.dtype, Tq, q.shape[3]):
+        raise C.OQError(f"{fn}: q {q.dtype} with head_dim {q.shape[3]} (bfloat16 with head_dim 64 or 128; decode_attention "
+                        "serves the rest)")
+    ws_n = C.size_call("oq_attn_extend_workspace", bs, nh, nkv, Tq, int(L), q.shape[3])
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_n:
+        workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
+    q = q.contiguous()
+    o = torch.empty_like(q) if out is None else out
+    return q, lengths, o, workspace, workspace.numel() * workspace.element_size()
+
+
+def extend_attention(q, k_cache, v_cache, L, scale, lengths, page_table=None, out=None, workspace=None):
+    """Chunked-prefill attention: decode_attention's ragged form for steps of MANY query rows over a cache that has a past
+    (csrc/oq_extend.hip: bf16 MFMA, 64-row K/V tiles through LDS shared by a GQA group's query heads, fp32 online softmax).
+    q [bs, Tq, nh, hd] bfloat16, hd 64 or 128; caches [bs, nkv, cap, hd] bfloat16; lengths (required) int32 [bs] on the device,
+    the rows of each sequence BEFORE this step's append; L an upper bound of lengths[b] + Tq, L <= cap.  Query row t of
+    sequence b attends rows j <= lengths[b] + t; rows at or beyond lengths[b] + Tq are never read.  There is no mask.
+    page_table: as in decode_attention (oq_attn_extend_paged), bit-identical to the slab call on the same rows."""
+    bs, Tq, nh, hd = q.shape
+    pages = None
+    if page_table is not None:
+        if not torch.is_tensor(k_cache) or k_cache.dim() != 4:
+            raise C.OQError("extend_attention: page_table needs the page pools [num_pages, nkv, PS, hd] as k_cache / v_cache")
+        nkv = k_cache.shape[1]
+        pages = _page_pool("extend_attention", page_table, lengths, 0, None, bs, nkv, ((k_cache, hd, q.dtype), (v_cache, hd, q.dtype)))
+        cap = pages[1] * pages[3]
+    else:
+        if k_cache.dim() != 4 or tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
+                or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+            raise C.OQError(f"extend_attention: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
+        nkv, cap = k_cache.shape[1], k_cache.shape[2]
+    q, lengths, o, workspace, ws_n = _extend_args("extend_attention", q, lengths, bs, k_cache.device, Tq, L, cap, nh, nkv, out, workspace)
+    if pages:
+        C.call("oq_attn_extend_paged", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd,
+               C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace), ws_n, C.stream())
+        return o
+    C.call("oq_attn_extend", C.ptr(q), C.ptr(k_cache), C.ptr(v_cache), C.ptr(o), C.dt(q), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths),
+           int(L), float(scale), C.ptr(workspace), ws_n, C.stream())
+    return o
+
+
+def extend_attention_codes(q, cache, L, scale, lengths, page_table=None, out=None, workspace=None):
+    """extend_attention over a 4-bit code cache (oq_attn_extend_codes): `cache` is a cache with code_bits 4 or its (k_codes,
+    v_codes, k_meta, v_meta) buffers.  A row enters the MFMA as code - zero_point; its scale multiplies the score (K) and the
+    probability (V) once per row, as in decode_attention_codes.  page_table: the buffers are page pools
+    (oq_attn_extend_codes_paged)."""
+    bs, Tq, nh, hd = q.shape
+    bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
+    if len(bufs) != 4 or not torch.is_tensor(bufs[0]) or bufs[0].dim() != 4:
+        raise C.OQError("extend_attention_codes: (k_codes, v_codes, k_meta, v_meta) buffers or page pools expected")
+    nkv = bufs[0].shape[1]
+    pages = None
+    if page_table is not None:
+        if hd not in (64, 128):
+            raise C.OQError(f"extend_attention_codes: head_dim {hd} (a code cache covers 64 and 128)")
+        pages = _page_pool("extend_attention_codes", page_table, lengths, 0, None, bs, nkv,
+                           ((bufs[0], hd // 2, torch.uint8), (bufs[1], hd // 2, torch.uint8), (bufs[2], 2, torch.float32),
+                            (bufs[3], 2, torch.float32)))
+        cap = pages[1] * pages[3]
+    else:
+        if bufs[0].shape[0] != bs:
+            raise C.OQError(f"extend_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
+        cap = _code_buffers("extend_attention_codes", *bufs, bs, nkv, hd)
+    q, lengths, o, workspace, ws_n = _extend_args("extend_attention_codes", q, lengths, bs, bufs[0].device, Tq, L, cap, nh, nkv, out,
+                                                  workspace)
+    if pages:
+        C.call("oq_attn_extend_codes_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+               C.dt(q), bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
+               ws_n, C.stream())
+        return o
+    C.call("oq_attn_extend_codes", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
+           bs, Tq, nh, nkv, hd, cap, C.ptr(lengths), int(L), float(scale), C.ptr(workspace), ws_n, C.stream())
+    return o
+
+
 def mask_is_causal(attention_mask):
     """True iff the additive attention mask ([T,T] or [bs,1,T,T]) is exactly the causal one: 0 on/below the diagonal
     and <= -3e4 above it -- finfo(float32).min, or finfo(float16).min = -65504 as transformers builds it for the fp16

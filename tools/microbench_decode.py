@@ -32,8 +32,17 @@
    median / min / max per kernel, the contiguous kernel's run-to-run spread (max - min over its median) and the ratios of
    the medians.  Then the three appends' paged forms next to their ragged forms at Tq = 1 (bound 8192).
 
+6. `--extend`: instead of 1 and 2, the MFMA chunked-prefill kernel (csrc/oq_extend.hip, oq_attn_extend*) against the ragged
+   decode kernel on the same inputs: one sequence with a past of 2048 and of 8192 rows, Tq = 16, 64, 256 and 1024 query
+   rows, at the 7B (32 / 32) and the 70B GQA (64 / 8) shape, on a bf16 slab, on bf16 pools of 16-row pages in a random page
+   order and on a 4-bit code slab.  The six graphs of a row (decode and extend per storage, the same cold cache sets for
+   both) are replayed alternately `--rounds` times; a row reports median / min / max per kernel, each decode kernel's
+   run-to-run spread (max - min over its median) and extend over decode.  `slower_beyond_spread` names the storage kinds
+   where the new kernel's median exceeds the decode kernel's by more than that spread: block_common.EXTEND_MIN_TQ must lie
+   above every Tq that has one.  FLOPs are not reported here: a share of the MFMA peak wants a counter run of its own.
+
 usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
-                                         [--codes | --ragged | --paged [--rounds 7]]
+                                         [--codes | --ragged | --paged | --extend [--rounds 7]]
 """
 import argparse
 import json
@@ -345,6 +354,71 @@ def paged_rows(reps, rounds, quick, dev):
     return rows
 
 
+EXTEND_TQ = [16, 64, 256, 1024]
+EXTEND_PAST = [2048, 8192]
+
+
+def extend_rows(reps, rounds, quick, dev):
+    rows = []
+    bs, ps = 1, 16
+    for name, nh, nkv, hd in SHAPES:
+        scale = hd ** -0.5
+        for past in EXTEND_PAST:
+            for Tq in EXTEND_TQ:
+                if quick and (past != 2048 or Tq not in (16, 256)):
+                    continue
+                L = past + Tq
+                lens = torch.tensor([past], dtype=torch.int32, device=dev)
+                q = torch.randn(bs, Tq, nh, hd, device=dev).bfloat16()
+                o = torch.empty_like(q)
+                ws = torch.empty(max(C.size_call("oq_attn_decode_workspace", bs, nh, nkv, Tq, L, hd),
+                                     C.size_call("oq_attn_extend_workspace", bs, nh, nkv, Tq, L, hd), 16), dtype=torch.uint8, device=dev)
+                kv_bytes, code_bytes = 2 * nkv * L * hd * 2, 2 * nkv * L * (hd // 2 + 8)
+                nsets = max(2, -(-COLD_BYTES // kv_bytes))
+                mp = -(-L // ps)
+
+                def meta(lead):
+                    m = torch.empty(*lead, 2, device=dev)
+                    m[..., 0] = torch.rand(*lead, device=dev) * 0.1 + 0.3
+                    m[..., 1] = torch.randint(5, 11, tuple(lead), device=dev).float()
+                    return m
+
+                slabs = [tuple(torch.randn(bs, nkv, L, hd, device=dev).bfloat16() for _ in range(2)) for _ in range(nsets)]
+                pools = [tuple(torch.randn(mp, nkv, ps, hd, device=dev).bfloat16() for _ in range(2)) for _ in range(nsets)]
+                tables = [torch.randperm(mp, generator=torch.Generator().manual_seed(i)).to(torch.int32)[None].to(dev)
+                          for i in range(nsets)]
+                codes = [tuple(torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev) for _ in range(2))
+                         + (meta((bs, nkv, L)), meta((bs, nkv, L))) for _ in range(max(2, -(-COLD_BYTES // code_bytes)))]
+                kw = dict(out=o, workspace=ws)
+                launches = (
+                    [(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, lengths=lens, **kw)) for s in slabs],
+                    [(lambda s=s: ops.extend_attention(q, s[0], s[1], L, scale, lens, **kw)) for s in slabs],
+                    [(lambda s=s, t=t: ops.decode_attention(q, s[0], s[1], L, scale, lengths=lens, page_table=t, **kw))
+                     for s, t in zip(pools, tables)],
+                    [(lambda s=s, t=t: ops.extend_attention(q, s[0], s[1], L, scale, lens, page_table=t, **kw))
+                     for s, t in zip(pools, tables)],
+                    [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, lengths=lens, **kw)) for s in codes],
+                    [(lambda s=s: ops.extend_attention_codes(q, s, L, scale, lens, **kw)) for s in codes])
+                us, med = interleaved(launches, reps, rounds)
+                r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, past=past, Tq=Tq, L_bound=L, dtype="bfloat16", cache="cold",
+                         rounds=rounds, sets=nsets, code_sets=len(codes), kv_bytes=kv_bytes, code_bytes=code_bytes)
+                slower = []
+                for i, k in enumerate(("slab", "paged16", "codes")):
+                    d, e = 2 * i, 2 * i + 1
+                    spread = (max(us[d]) - min(us[d])) / med[d]
+                    r.update({k + "_decode_us": med[d], k + "_decode_us_min": min(us[d]), k + "_decode_us_max": max(us[d]),
+                              k + "_decode_spread": spread, k + "_extend_us": med[e], k + "_extend_us_min": min(us[e]),
+                              k + "_extend_us_max": max(us[e]), k + "_extend_over_decode": med[e] / med[d]})
+                    if med[e] > med[d] * (1.0 + spread):
+                        slower.append(k)
+                r["slower_beyond_spread"] = slower
+                rows.append(r)
+                print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+                del launches, slabs, pools, codes
+                torch.cuda.empty_cache()
+    return rows
+
+
 def packed_7b_block(dev, L_cap):
     """A LLaMA-7B block with random W4 g128 AutoGPTQ buffers (the decode step's cost does not depend on their values)."""
     from omniquant_amd.calibrate import decoder_layer_class, default_args
@@ -445,7 +519,8 @@ def main():
     ap.add_argument("--codes", action="store_true", help="the code-cache kernel interleaved with the bf16-cache kernel")
     ap.add_argument("--ragged", action="store_true", help="ragged-batch kernels interleaved with the padded, masked ones")
     ap.add_argument("--paged", action="store_true", help="paged kernels interleaved with the ragged contiguous ones")
-    ap.add_argument("--rounds", type=int, default=7, help="--codes / --ragged / --paged: alternating replays of the graphs")
+    ap.add_argument("--extend", action="store_true", help="the MFMA chunked-prefill kernel interleaved with the ragged decode kernel")
+    ap.add_argument("--rounds", type=int, default=7, help="--codes / --ragged / --paged / --extend: alternating replays of the graphs")
     a = ap.parse_args()
     dev = "cuda:0"
     if not torch.cuda.is_available():
@@ -454,7 +529,9 @@ def main():
     if a.step_only:
         block_step(dev, a.reps, steps_only=a.steps)
         return
-    if a.paged:
+    if a.extend:
+        rows = extend_rows(a.reps, a.rounds, a.quick, dev)
+    elif a.paged:
         rows = paged_rows(a.reps, a.rounds, a.quick, dev)
     elif a.ragged:
         rows = ragged_rows(a.reps, a.rounds, dev)
