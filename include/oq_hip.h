@@ -477,6 +477,53 @@ int oq_attn_extend_codes_paged(const void* q, const void* k_codes, const void* v
                                void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
                                int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
                                float scale, void* workspace, int64_t workspace_bytes, void* stream);
+/*   8-bit code cache (weight-only blocks, whose k / v sit on no grid; models/int_llama_layer.py:121-135,143-163,177 and
+ *      models/int_opt_layer.py:110-121,151-170 are what the cache stands in for, quantize/quantizer.py:122-147 the quantiser):
+ *      K and V as codes uint8 [bs, nkv, cap, hd], byte d of a row holding dim d, plus meta f32 [bs, nkv, cap, 2] = (scale,
+ *      rounded zero-point) per row; a stored element's value is fp32((code - zp) * scale).  The quantiser is the asymmetric
+ *      per-(token, head) one of oq_kv_append_quant at 8 bits, over the fp32 post-rotation k and over v, with the row range
+ *      widened to contain zero (lo = min(lo, 0), hi = max(hi, 0)): zp lies in [0, 255], so code - zp is exact in bf16; a row
+ *      with lo < 0 < hi gets the codes and values of oq_kv_append_quant(nbits 8); a row whose scale comes out as 0 (all zeros)
+ *      is stored as codes 0 under meta (0, 0) and reads back as zeros; a row with a NaN or infinite element, or whose range
+ *      overflows, is stored as codes 0 under a NaN scale.  q is rotated and NOT quantised: q_out has oq_kv_append's bits.
+ *   oq_kv_append_codes8 / _ragged / _paged: the argument lists of oq_kv_append_quant_codes / _ragged / _paged without nbits,
+ *      with their row range, skipping and page rules.  k_out / v_out (both or neither) receive the DEQUANTISED values rounded
+ *      once to dtype: what every later step reads from the cache.  in_dtype f32 or dtype, dtype f32 / bf16, hd 64 / 128.
+ *   oq_attn_decode_codes8 / _ragged / _paged: oq_attn_decode_codes / _ragged / _paged over such a cache: the same loops, sums,
+ *      split plan, workspace, mask handling and rounding points, K and V dequantised in registers in the factored form.
+ *   oq_attn_extend_codes8 / _paged: oq_attn_extend_codes / _paged over such a cache (bf16, head_dim 64 / 128). */
+int oq_kv_append_codes8(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                        void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq, int nh,
+                        int nkv, int hd, int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P,
+                        const int64_t* pos, int64_t pos_bstride, void* stream);
+int oq_kv_append_codes8_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                               void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq,
+                               int nh, int nkv, int hd, int64_t cap, const int32_t* lens, const float* cos, const float* sin,
+                               int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream);
+int oq_kv_append_codes8_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                              void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq,
+                              int nh, int nkv, int hd, const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                              const int32_t* lens, const float* cos, const float* sin, int64_t P, const int64_t* pos,
+                              int64_t pos_bstride, void* stream);
+int oq_attn_decode_codes8(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta, void* o,
+                          int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, float scale,
+                          const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int oq_attn_decode_codes8_ragged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                                 void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                                 const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
+int oq_attn_decode_codes8_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                                void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                                int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
+                                float scale, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_attn_extend_codes8(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta, void* o,
+                          int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens,
+                          int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes, void* stream);
+int oq_attn_extend_codes8_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                                void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
+                                int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
+                                float scale, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using

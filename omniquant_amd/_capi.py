@@ -109,6 +109,22 @@ SIGNATURES = {
                              _i64, _vp],
     "oq_attn_extend_codes_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
                                    _i64, _f32, _vp, _i64, _vp],
+    # 8-bit code cache of the weight-only blocks: the 4-bit code forms' argument lists without nbits
+    "oq_kv_append_codes8": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64,
+                            _vp, _vp, _i64, _vp, _i64, _vp],
+    "oq_kv_append_codes8_ragged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32,
+                                   _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
+    "oq_kv_append_codes8_paged": [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32,
+                                  _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
+    "oq_attn_decode_codes8": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _f32, _vp, _i32, _i64, _i64,
+                              _vp, _i64, _vp],
+    "oq_attn_decode_codes8_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp,
+                                     _i64, _vp],
+    "oq_attn_decode_codes8_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
+                                    _i64, _f32, _vp, _i64, _vp],
+    "oq_attn_extend_codes8": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
+    "oq_attn_extend_codes8_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
+                                    _i64, _f32, _vp, _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,

@@ -75,7 +75,10 @@ class QuantBlockMixin:
         A block packed with kv_cache_bits=4 creates, and converts tuples into, 4-bit code caches; a caller's PackedKVCache of
         either kind is taken as it is (an empty pre-sized code cache switches an unmarked W4A4 block to codes), except that a
         code cache needs the head quantisers (head_bits 4).  So is a caller's PagedKVCache (paged, ragged storage); a block never
-        creates one by itself."""
+        creates one by itself.
+        A weight-only block (head_bits None) packed with kv_cache_bits=8 creates, and converts tuples into, 8-bit code caches,
+        and takes a caller's 8-bit code cache whether marked or not; a W4A4 block refuses one, as a weight-only block refuses
+        a 4-bit one."""
         from ._capi import OQError
         from .kvcache import PackedKVCache, PagedKVCache
         if hd not in (64, 128):
@@ -87,7 +90,11 @@ class QuantBlockMixin:
             c = past_key_value
             if (c.bs, c.nkv, c.hd) != (bsz, nkv, hd) or c.dtype != x.dtype or c.device != x.device:
                 raise OQError(f"{c!r} does not fit this block's step: batch {bsz}, {nkv} kv heads of {hd}, {x.dtype} on {x.device}")
-            if c.code_bits is not None and head_bits != c.code_bits:
+            if c.code_bits == 8:
+                if head_bits is not None:
+                    raise OQError(f"{c!r}: code_bits 8 is the weight-only blocks' cache (this W4A4 block's k / v sit on its "
+                                  f"{head_bits}-bit head grid: code_bits 4)")
+            elif c.code_bits is not None and head_bits != c.code_bits:
                 raise OQError(f"{c!r}: code_bits {c.code_bits} needs a W4A4 block (this block's k / v are not on a 4-bit grid)")
             return c
         if isinstance(past_key_value, (tuple, list)) and len(past_key_value) == 2:
@@ -150,6 +157,9 @@ class QuantBlockMixin:
         width in the append's launch, so the cache holds, and the attention reads, the quantised values in the cache's dtype.
         A code cache (cache.code_bits 4) receives the codes instead (oq_kv_append_quant_codes) and steps with a past run
         oq_attn_decode_codes on them; its prefill runs the same attention launches on the same q / k / v values.
+        An 8-bit code cache (cache.code_bits 8; weight-only blocks, head_bits None): k / v pass the cache's own 8-bit quantiser
+        in the append's launch (oq_kv_append_codes8; q is only rotated) and the prefill attends the DEQUANTISED rows (k_out /
+        v_out), which is what every later step reads from the cache (oq_attn_decode_codes8 / oq_attn_extend_codes8).
         A ragged cache (cache.ragged): the append and the attention read the same pre-step cache.lengths on the device
         (lengths= of the ops), `past` and L are host bounds, and the step's rows are right-padded: new_tokens = (counts or None
         for all Tq, growth of the bound, the counts on the host or None) from _new_tokens_in says how many rows of each sequence
@@ -181,7 +191,13 @@ class QuantBlockMixin:
         cache.reserve(Tq)
         rot = cos is not None
         # copies of this step's rows for the prefill's attention, of every tensor the append changes
-        if head_bits is None:
+        if head_bits is None and cache.code_bits == 8:
+            qr = torch.empty_like(q) if rot else q
+            kr, vr = (torch.empty_like(k), torch.empty_like(v)) if past == 0 else (None, None)
+            ops.kv_append_codes(k, v, cache.dtype, cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta,
+                                past=0 if cache.ragged else past, q=q if rot else None, q_out=qr if rot else None, k_out=kr,
+                                v_out=vr, cos=cos, sin=sin, positions=positions, lengths=lens, **paged)
+        elif head_bits is None:
             qr = torch.empty_like(q) if rot else q
             kr, vr = torch.empty_like(k) if (rot and past == 0) else None, None
             ops.kv_append(k, v, cache.k, cache.v, 0 if cache.ragged else past, q=q if rot else None, q_out=qr if rot else None,

@@ -1,7 +1,9 @@
 // Incremental-decoding kernels of the packed (real-quant) blocks on gfx950: the KV-cache append with RoPE at arbitrary
 // positions (one kernel template; its QUANT instantiations add the W4A4 head quantisers and serve oq_kv_append_quant, its
-// CODES instantiations also store the 4-bit codes: oq_kv_append_quant_codes), and attention of 1..Tq query rows against
-// the cached K/V, held as floats (oq_attn_decode) or as 4-bit codes (oq_attn_decode_codes).
+// CODES instantiations also store the 4-bit codes: oq_kv_append_quant_codes; CODES = 8 quantises k and v alone, on a 255-level
+// grid whose range contains zero, for the weight-only blocks: oq_kv_append_codes8), and attention of 1..Tq query rows against
+// the cached K/V, held as floats (oq_attn_decode), as 4-bit codes (oq_attn_decode_codes) or as 8-bit codes
+// (oq_attn_decode_codes8).
 // Reference lines: models/int_llama_layer.py:121-135,177 (rotary embedding gathered at position_ids, torch.cat with
 // past_key_value, present_key_value) and :143-163 (scores, mask, softmax, PV); models/int_opt_layer.py:110-121,151-170.
 //
@@ -36,8 +38,9 @@ struct AppendP {
     int64_t pos_bs;
     int nbits;
     float inv_q;
-    // code destination (CODES instantiations, 4-bit): rows of hd / 2 bytes, dim d in nibble d % 8 of the little-endian
-    // 32-bit word d / 8, and one (scale, rounded zero-point) pair per row; value = (code - zp) * scale
+    // code destination (CODES instantiations): 4-bit rows of hd / 2 bytes, dim d in nibble d % 8 of the little-endian
+    // 32-bit word d / 8, or 8-bit rows of hd bytes, dim d in byte d; and one (scale, rounded zero-point) pair per row;
+    // value = (code - zp) * scale
     uint8_t *k_codes, *v_codes;
     float *k_meta, *v_meta;
     // RAGGED instantiations: the rows before this step, per sequence, int32 [bs] on the device (`past` is not read)
@@ -51,7 +54,10 @@ struct AppendP {
 // never clamped onto another row); its q_out / k_out / v_out rows are written like any other.
 // PAGED (a form of RAGGED): that logical row goes through the page table; a row whose table entry is outside [0, num_pages)
 // is skipped in the same way (the entry of a row outside [0, cap) is not read).
-template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED, bool PAGED>
+// CODES: 0 (float rows), 4 or 8, the width of the codes stored.  CODES == 8 (weight-only blocks; QUANT is set): the q slot takes
+// the plain path, and the k / v slots pass the 8-bit asymmetric quantiser with the row range widened to contain zero (zp in
+// [0, 255]); a row whose scale comes out as 0 (all zeros) is stored as codes 0 under meta (0, 0) and reads back as zeros.
+template <typename TIN, typename T, bool QUANT, int CODES, bool RAGGED, bool PAGED>
 __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     static_assert(RAGGED || !PAGED, "paged storage is always ragged");
     const int hd = p.hd, nh = p.nh, nkv = p.nkv;
@@ -62,6 +68,7 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     const TIN* v = (const TIN*)p.v;
     T *q_out = (T*)p.q_out, *k_out = (T*)p.k_out, *v_out = (T*)p.v_out, *kc = (T*)p.kc, *vc = (T*)p.vc;
     const int half = hd / 2, hv = hd / 16;
+    const int cbytes = CODES == 8 ? hd : half;                       // bytes of a code row
     const int nslot = nh + 2 * nkv;
     const int64_t n = p.bs * Tq * nslot * hv;
     for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) {
@@ -103,8 +110,8 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
             src = k + ((b * Tq + t) * nkv + h) * hd;
             dst = kc && fits ? kc + crow(h) * hd : nullptr;
             dst2 = k_out ? k_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
-            if constexpr (CODES) {
-                cdst = fits ? p.k_codes + crow(h) * half : nullptr;
+            if constexpr (CODES != 0) {
+                cdst = fits ? p.k_codes + crow(h) * cbytes : nullptr;
                 mdst = p.k_meta + crow(h) * 2;
             }
         } else {
@@ -112,8 +119,8 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
             src = v + ((b * Tq + t) * nkv + h) * hd;
             dst = vc && fits ? vc + crow(h) * hd : nullptr;
             dst2 = v_out ? v_out + ((b * Tq + t) * nkv + h) * hd : nullptr;
-            if constexpr (CODES) {
-                cdst = fits ? p.v_codes + crow(h) * half : nullptr;
+            if constexpr (CODES != 0) {
+                cdst = fits ? p.v_codes + crow(h) * cbytes : nullptr;
                 mdst = p.v_meta + crow(h) * 2;
             }
             rot = false;
@@ -134,7 +141,59 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) { a[i] = oa[i]; c[i] = ob[i]; }
         }
-        if constexpr (QUANT) {
+        if constexpr (CODES == 8) {
+            // every lane of the (token, head) group reduces; the q slot then leaves its values alone
+            float hi = 0.f, lo = 0.f, bad = 0.f;                    // the range contains zero
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                hi = fmaxf(hi, fmaxf(a[i], c[i]));
+                lo = fminf(lo, fminf(a[i], c[i]));
+                if (a[i] != a[i] || c[i] != c[i]) bad = 1.f;
+            }
+            hi = wave_max(hi, hv);
+            lo = wave_min(lo, hv);
+            bad = wave_max(bad, hv);
+            if (slot >= nh) {
+                if (bad != 0.f) { hi = NAN; lo = NAN; }
+                float inv_s = 0.f;
+                const QP qp = make_qp(hi, lo, false, 0.f, 0.f, 8, 0, p.inv_q, &inv_s);
+                const bool zero = qp.s == 0.f;                      // an all-zero row (or a range that underflows): exact zeros
+                const bool finite = fabsf(qp.s) <= 3.4028234663852886e38f;
+                const bool regular = !zero && finite && bad == 0.f && fabsf(inv_s) <= 3.4028234663852886e38f;
+                float ca[8], cc[8];                                 // the lane's 16 codes
+                float nan_row = finite ? 0.f : 1.f;                 // a NaN / inf element or an overflowing range
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    float& x = i < 8 ? a[i] : c[i - 8];
+                    float code = 0.f;
+                    if (regular) {
+                        float tq;
+                        const float rq = rne_div(x, qp.s, inv_s, &tq);
+                        code = __builtin_amdgcn_fmed3f(rq + qp.z, 0.f, 255.f);
+                        x = (code - qp.z) * qp.s;
+                    } else if (zero) {
+                        x = 0.f;
+                    } else {                                        // a subnormal scale: the exact division
+                        float u = rne_ste(x / qp.s) + qp.z;
+                        u = (u != u) ? u : fminf(fmaxf(u, 0.f), 255.f);
+                        x = (u - qp.z) * qp.s;
+                        if (u != u) nan_row = 1.f;
+                        else code = u;
+                    }
+                    (i < 8 ? ca[i] : cc[i - 8]) = code;
+                }
+                nan_row = wave_max(nan_row, hv);
+                if (nan_row != 0.f) {                               // codes 0 under a NaN scale, as the 4-bit rows
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) { a[i] = NAN; c[i] = NAN; ca[i] = 0.f; cc[i] = 0.f; }
+                }
+                if (cdst) {
+                    oq_store_codes8(reinterpret_cast<int8_t*>(cdst + d0), ca, false);
+                    oq_store_codes8(reinterpret_cast<int8_t*>(cdst + half + d0), cc, false);
+                    if (d0 == 0) *reinterpret_cast<f32x2*>(mdst) = f32x2{nan_row != 0.f ? NAN : qp.s, zero ? 0.f : qp.z};
+                }
+            }
+        } else if constexpr (QUANT) {
             const float Q = (float)((1 << p.nbits) - 1);
             float hi = -INFINITY, lo = INFINITY, bad = 0.f;
 #pragma unroll
@@ -163,18 +222,18 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
                     const float rq = rne_div(x, qp.s, inv_s, &tq);
                     const float code = __builtin_amdgcn_fmed3f(rq + qp.z, 0.f, Q);
                     x = (code - qp.z) * qp.s;
-                    if constexpr (CODES) (i < 8 ? wa : wc) |= (uint32_t)code << (4 * (i & 7));
+                    if constexpr (CODES != 0) (i < 8 ? wa : wc) |= (uint32_t)code << (4 * (i & 7));
                 } else {
                     float u = rne_ste(x / qp.s) + qp.z;
                     u = (u != u) ? u : fminf(fmaxf(u, 0.f), Q);
                     x = (u - qp.z) * qp.s;
-                    if constexpr (CODES) {
+                    if constexpr (CODES != 0) {
                         if (u != u) nan_row = 1.f;
                         else (i < 8 ? wa : wc) |= (uint32_t)u << (4 * (i & 7));
                     }
                 }
             }
-            if constexpr (CODES) {
+            if constexpr (CODES != 0) {
                 // a row of scale 0, inf or NaN (constant rows, overflowing ranges, NaN inputs) comes out of the branch above as
                 // NaN in every element: codes 0 under a NaN scale hold exactly that.  Every other row has no NaN at all.
                 nan_row = wave_max(nan_row, hv);
@@ -197,7 +256,7 @@ __global__ void __launch_bounds__(256) kv_append_kernel(AppendP p) {
     }
 }
 
-template <typename TIN, typename T, bool QUANT, bool CODES, bool RAGGED, bool PAGED>
+template <typename TIN, typename T, bool QUANT, int CODES, bool RAGGED, bool PAGED>
 void launch_append(const AppendP& p, hipStream_t st) {
     const int64_t n = p.bs * p.Tq * (p.nh + 2 * p.nkv) * (p.hd / 16);
     const int64_t grid = (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096;
@@ -206,7 +265,7 @@ void launch_append(const AppendP& p, hipStream_t st) {
 
 // The checks, the grid and the dtype dispatch both ABI entry points share (fn: the entry point's name for the messages).
 // The caller has checked what is its own: which pointers it requires, head_dim, nbits and the dtype pairs it admits.
-template <bool QUANT, bool CODES = false, bool RAGGED = false, bool PAGED = false>
+template <bool QUANT, int CODES = 0, bool RAGGED = false, bool PAGED = false>
 int kv_append(const char* fn, const AppendP& p, int in_dtype, int dtype, void* stream) {
     OQ_CHECK_ARG(!p.q || p.q_out, "%s: q without q_out", fn);
     OQ_CHECK_ARG(p.bs > 0 && p.Tq > 0 && p.nkv > 0 && p.nh >= 0 && (p.q || p.nh == 0), "%s: bad shape", fn);
@@ -325,7 +384,53 @@ struct CodeKV {
     }
 };
 
-// Either of the two over a page pool [num_pages, nkv, PS, ...]: the same rows, registers and arithmetic, found through the
+// 8-bit code cache: rows of HD code bytes (dim d in byte d) plus the (scale, zero-point) pair, value = (code - zp) * scale with
+// zp in [0, 255].  A lane holds DPL dims: DPL / 4 words, one 8- or 16-byte load; unpack and scale are CodeKV's contract.
+template <int HD, int DPL_>
+struct Code8KV {
+    static constexpr int DPL = DPL_;
+    static constexpr bool SCALED = true;
+    static constexpr bool PAGED = false;
+    static constexpr int W = DPL / 4;
+    const uint8_t *k, *v;
+    const f32x2 *km, *vm;
+    struct Row {
+        uint32_t w[W];
+        f32x2 m;
+        __device__ __forceinline__ void load(const uint8_t* p) {
+            if constexpr (W == 4) {
+                const u32x4 r = *reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+                for (int n = 0; n < 4; ++n) w[n] = r[n];
+            } else {
+                typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+                const u32x2 r = *reinterpret_cast<const u32x2*>(p);
+                w[0] = r[0];
+                w[1] = r[1];
+            }
+        }
+        __device__ __forceinline__ void unpack(float (&o)[DPL]) const {
+#pragma unroll
+            for (int n = 0; n < W; ++n)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[4 * n + i] = (float)((w[n] >> (8 * i)) & 0xFFu) - m[1];      // v_cvt_f32_ubyte<i>
+        }
+        __device__ __forceinline__ float scale() const { return m[0]; }
+    };
+    __device__ __forceinline__ Code8KV at(int64_t b, int kvh, int nkv, int64_t cap, int d0) const {
+        const int64_t row0 = (b * nkv + kvh) * cap;
+        return {k + row0 * HD + d0, v + row0 * HD + d0, km + row0, vm + row0};
+    }
+    __device__ __forceinline__ bool load(Row& kr, Row& vr, int64_t j) const {
+        kr.load(k + j * HD);
+        vr.load(v + j * HD);
+        kr.m = km[j];
+        vr.m = vm[j];
+        return true;
+    }
+};
+
+// Any of the three over a page pool [num_pages, nkv, PS, ...]: the same rows, registers and arithmetic, found through the
 // page table.  at() moves the inner view to this kv head's rows of page 0 and the table to sequence b's row; load() reads
 // the lane group's own table entry (a vector load: the groups of a wave hold different rows j) and then the row, PS
 // contiguous rows per (page, kv head).  Callers keep j below the bound L <= max_pages * PS, so the entry exists.
@@ -567,14 +672,15 @@ void launch_decode_float(int qb, const DecP& p, const void* kc, const void* vc, 
     launch_decode_qb<T, HD>(qb, p, kv, st);
 }
 
-// One or two query rows per pass leave the registers for 16 dims per lane (8-byte loads); four or eight keep 8 dims.
-template <typename T, int HD>
+// One or two query rows per pass leave the registers for 16 dims per lane (4-bit: 8-byte loads, 8-bit: 16-byte loads); four or
+// eight keep 8 dims.  CKV: CodeKV or Code8KV.
+template <typename T, int HD, template <int, int> class CKV>
 void launch_decode_codes(int qb, const DecP& p, const void* kc, const void* vc, const float* km, const float* vm, hipStream_t st) {
-    const CodeKV<HD, 16> wide{(const uint8_t*)kc, (const uint8_t*)vc, (const f32x2*)km, (const f32x2*)vm};
-    const CodeKV<HD, 8> narrow{wide.k, wide.v, wide.km, wide.vm};
+    const CKV<HD, 16> wide{(const uint8_t*)kc, (const uint8_t*)vc, (const f32x2*)km, (const f32x2*)vm};
+    const CKV<HD, 8> narrow{wide.k, wide.v, wide.km, wide.vm};
     if (p.pm.table) {
-        if (qb <= 2) launch_decode_qb<T, HD>(qb, p, PagedKV<CodeKV<HD, 16>>{wide, p.pm, 0}, st);
-        else launch_decode_qb<T, HD>(qb, p, PagedKV<CodeKV<HD, 8>>{narrow, p.pm, 0}, st);
+        if (qb <= 2) launch_decode_qb<T, HD>(qb, p, PagedKV<CKV<HD, 16>>{wide, p.pm, 0}, st);
+        else launch_decode_qb<T, HD>(qb, p, PagedKV<CKV<HD, 8>>{narrow, p.pm, 0}, st);
     } else if (qb <= 2) {
         launch_decode_qb<T, HD>(qb, p, wide, st);
     } else {
@@ -592,8 +698,8 @@ int append_plain(const char* fn, const void* q, const void* k, const void* v, vo
     OQ_CHECK_ARG(hd > 0 && hd % 16 == 0, "%s: head_dim %d must be a multiple of 16", fn, hd);
     const AppendP p{q, k, v, q_out, k_out, nullptr, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
                     0, 0.f, nullptr, nullptr, nullptr, nullptr, lens, pm};
-    if (pm.table) return kv_append<false, false, true, true>(fn, p, dtype, dtype, stream);
-    return lens ? kv_append<false, false, true>(fn, p, dtype, dtype, stream) : kv_append<false>(fn, p, dtype, dtype, stream);
+    if (pm.table) return kv_append<false, 0, true, true>(fn, p, dtype, dtype, stream);
+    return lens ? kv_append<false, 0, true>(fn, p, dtype, dtype, stream) : kv_append<false>(fn, p, dtype, dtype, stream);
 }
 
 int append_quant(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
@@ -610,30 +716,34 @@ int append_quant(const char* fn, const void* q, const void* k, const void* v, in
     OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
     const AppendP p{q, k, v, q_out, k_out, v_out, k_cache, v_cache, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
                     nbits, 1.0f / (float)((1 << nbits) - 1), nullptr, nullptr, nullptr, nullptr, lens, pm};
-    if (pm.table) return kv_append<true, false, true, true>(fn, p, in_dtype, dtype, stream);
-    return lens ? kv_append<true, false, true>(fn, p, in_dtype, dtype, stream) : kv_append<true>(fn, p, in_dtype, dtype, stream);
+    if (pm.table) return kv_append<true, 0, true, true>(fn, p, in_dtype, dtype, stream);
+    return lens ? kv_append<true, 0, true>(fn, p, in_dtype, dtype, stream) : kv_append<true>(fn, p, in_dtype, dtype, stream);
 }
 
 int append_codes(const char* fn, const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
                  void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq, int nh, int nkv,
                  int hd, int64_t cap, int64_t past, const int32_t* lens, const PageMap& pm, const float* cos, const float* sin,
-                 int64_t P, const int64_t* pos, int64_t pos_bstride, int nbits, void* stream) {
+                 int64_t P, const int64_t* pos, int64_t pos_bstride, int cbits, int nbits, void* stream) {
     OQ_CHECK_ARG(k && v && k_codes && v_codes && k_meta && v_meta, "%s: null pointer", fn);
     OQ_CHECK_ARG(hd == 64 || hd == 128, "%s: head_dim %d (64 or 128)", fn, hd);
-    OQ_CHECK_ARG(nbits == 4, "%s: %d-bit codes (4)", fn, nbits);
+    OQ_CHECK_ARG(nbits == cbits, "%s: %d-bit codes (%d)", fn, nbits, cbits);
     OQ_CHECK_ARG(dtype == OQ_F32 || dtype == OQ_BF16, "%s: dtype %d (f32 or bf16)", fn, dtype);
     OQ_CHECK_ARG(in_dtype == OQ_F32 || in_dtype == dtype, "%s: input dtype %d (f32 or the output dtype)", fn, in_dtype);
     OQ_CHECK_ARG(!k_out == !v_out, "%s: k_out and v_out go together", fn);
     const AppendP p{q, k, v, q_out, k_out, v_out, nullptr, nullptr, bs, Tq, nh, nkv, hd, cap, past, cos, sin, P, pos, pos_bstride,
-                    nbits, 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta, lens, pm};
-    if (pm.table) return kv_append<true, true, true, true>(fn, p, in_dtype, dtype, stream);
-    return lens ? kv_append<true, true, true>(fn, p, in_dtype, dtype, stream) : kv_append<true, true>(fn, p, in_dtype, dtype, stream);
+                    nbits, cbits == 8 ? 1.0f / 255.0f : 1.0f / 15.0f, (uint8_t*)k_codes, (uint8_t*)v_codes, k_meta, v_meta, lens, pm};
+    if (cbits == 8) {
+        if (pm.table) return kv_append<true, 8, true, true>(fn, p, in_dtype, dtype, stream);
+        return lens ? kv_append<true, 8, true>(fn, p, in_dtype, dtype, stream) : kv_append<true, 8>(fn, p, in_dtype, dtype, stream);
+    }
+    if (pm.table) return kv_append<true, 4, true, true>(fn, p, in_dtype, dtype, stream);
+    return lens ? kv_append<true, 4, true>(fn, p, in_dtype, dtype, stream) : kv_append<true, 4>(fn, p, in_dtype, dtype, stream);
 }
 
-// codes: k / v are the code buffers of a 4-bit cache and k_meta / v_meta its (scale, zero-point) pairs; else a float cache's
-// buffers (no meta).  ragged: lens is required and there is no mask; L is then the bound.  pm.table: the buffers are page
+// codes (0, 4 or 8): k / v are the code buffers of a cache of that width and k_meta / v_meta its (scale, zero-point) pairs; 0: a
+// float cache's buffers (no meta).  ragged: lens is required and there is no mask; L is then the bound.  pm.table: the buffers are page
 // pools and cap = max_pages * page size (ragged only).
-int decode(const char* fn, bool codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
+int decode(const char* fn, int codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
            int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, const int32_t* lens, bool ragged,
            const PageMap& pm, float scale, const void* mask, int mask_dtype, int64_t mask_bstride, int64_t mask_ld, void* workspace,
            int64_t workspace_bytes, void* stream) {
@@ -659,11 +769,16 @@ int decode(const char* fn, bool codes, const void* q, const void* k, const void*
         return OQ_E_UNSUPPORTED;
     }
     const bool f32 = dtype == OQ_F32;
-    if (codes) {
-        if (f32 && hd == 64) launch_decode_codes<float, 64>(qb, p, k, v, k_meta, v_meta, st);
-        else if (f32) launch_decode_codes<float, 128>(qb, p, k, v, k_meta, v_meta, st);
-        else if (hd == 64) launch_decode_codes<bf16_t, 64>(qb, p, k, v, k_meta, v_meta, st);
-        else launch_decode_codes<bf16_t, 128>(qb, p, k, v, k_meta, v_meta, st);
+    if (codes == 8) {
+        if (f32 && hd == 64) launch_decode_codes<float, 64, Code8KV>(qb, p, k, v, k_meta, v_meta, st);
+        else if (f32) launch_decode_codes<float, 128, Code8KV>(qb, p, k, v, k_meta, v_meta, st);
+        else if (hd == 64) launch_decode_codes<bf16_t, 64, Code8KV>(qb, p, k, v, k_meta, v_meta, st);
+        else launch_decode_codes<bf16_t, 128, Code8KV>(qb, p, k, v, k_meta, v_meta, st);
+    } else if (codes) {
+        if (f32 && hd == 64) launch_decode_codes<float, 64, CodeKV>(qb, p, k, v, k_meta, v_meta, st);
+        else if (f32) launch_decode_codes<float, 128, CodeKV>(qb, p, k, v, k_meta, v_meta, st);
+        else if (hd == 64) launch_decode_codes<bf16_t, 64, CodeKV>(qb, p, k, v, k_meta, v_meta, st);
+        else launch_decode_codes<bf16_t, 128, CodeKV>(qb, p, k, v, k_meta, v_meta, st);
     } else {
         if (f32 && hd == 64) launch_decode_float<float, 64>(qb, p, k, v, st);
         else if (f32) launch_decode_float<float, 128>(qb, p, k, v, st);
@@ -701,14 +816,14 @@ extern "C" int64_t oq_attn_decode_workspace(int64_t bs, int nh, int nkv, int64_t
 extern "C" int oq_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq,
                               int nh, int nkv, int hd, int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype,
                               int64_t mask_bstride, int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
-    return decode("oq_attn_decode", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
+    return decode("oq_attn_decode", 0, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
                   NO_PAGES, scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
 }
 
 extern "C" int oq_attn_decode_ragged(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs,
                                      int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound,
                                      float scale, void* workspace, int64_t workspace_bytes, void* stream) {
-    return decode("oq_attn_decode_ragged", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+    return decode("oq_attn_decode_ragged", 0, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
                   true, NO_PAGES, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
 
@@ -735,7 +850,7 @@ extern "C" int oq_kv_append_quant_codes(const void* q, const void* k, const void
                                         const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
                                         int nbits, void* stream) {
     return append_codes("oq_kv_append_quant_codes", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs,
-                        Tq, nh, nkv, hd, cap, past, nullptr, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        Tq, nh, nkv, hd, cap, past, nullptr, NO_PAGES, cos, sin, P, pos, pos_bstride, 4, nbits, stream);
 }
 
 extern "C" int oq_kv_append_quant_codes_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
@@ -745,14 +860,14 @@ extern "C" int oq_kv_append_quant_codes_ragged(const void* q, const void* k, con
                                                int64_t pos_bstride, int nbits, void* stream) {
     OQ_CHECK_ARG(lens, "oq_kv_append_quant_codes_ragged: null lens");
     return append_codes("oq_kv_append_quant_codes_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype,
-                        bs, Tq, nh, nkv, hd, cap, 0, lens, NO_PAGES, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        bs, Tq, nh, nkv, hd, cap, 0, lens, NO_PAGES, cos, sin, P, pos, pos_bstride, 4, nbits, stream);
 }
 
 extern "C" int oq_attn_decode_codes(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
                                     const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
                                     int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
                                     int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
-    return decode("oq_attn_decode_codes", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
+    return decode("oq_attn_decode_codes", 4, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
                   NO_PAGES, scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
 }
 
@@ -760,7 +875,7 @@ extern "C" int oq_attn_decode_codes_ragged(const void* q, const void* k_codes, c
                                            const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
                                            int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                            int64_t workspace_bytes, void* stream) {
-    return decode("oq_attn_decode_codes_ragged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+    return decode("oq_attn_decode_codes_ragged", 4, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
                   lens, true, NO_PAGES, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
 
@@ -793,7 +908,7 @@ extern "C" int oq_kv_append_quant_codes_paged(const void* q, const void* k, cons
                                               int64_t pos_bstride, int nbits, void* stream) {
     OQ_PAGE_MAP("oq_kv_append_quant_codes_paged");
     return append_codes("oq_kv_append_quant_codes_paged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype,
-                        bs, Tq, nh, nkv, hd, cap, 0, lens, pm, cos, sin, P, pos, pos_bstride, nbits, stream);
+                        bs, Tq, nh, nkv, hd, cap, 0, lens, pm, cos, sin, P, pos, pos_bstride, 4, nbits, stream);
 }
 
 extern "C" int oq_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, void* o, int dtype, int64_t bs, int64_t Tq,
@@ -801,7 +916,7 @@ extern "C" int oq_attn_decode_paged(const void* q, const void* k_pool, const voi
                                     int page_size, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
     OQ_PAGE_MAP("oq_attn_decode_paged");
-    return decode("oq_attn_decode_paged", false, q, k_pool, v_pool, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+    return decode("oq_attn_decode_paged", 0, q, k_pool, v_pool, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
                   true, pm, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
 
@@ -811,6 +926,61 @@ extern "C" int oq_attn_decode_codes_paged(const void* q, const void* k_codes, co
                                           const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
     OQ_PAGE_MAP("oq_attn_decode_codes_paged");
-    return decode("oq_attn_decode_codes_paged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+    return decode("oq_attn_decode_codes_paged", 4, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+                  lens, true, pm, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+}
+
+// ---- 8-bit code cache of the weight-only blocks: the entry points of the 4-bit one without nbits --------------------------------
+extern "C" int oq_kv_append_codes8(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out, void* v_out,
+                                   void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype, int64_t bs, int64_t Tq,
+                                   int nh, int nkv, int hd, int64_t cap, int64_t past, const float* cos, const float* sin, int64_t P,
+                                   const int64_t* pos, int64_t pos_bstride, void* stream) {
+    return append_codes("oq_kv_append_codes8", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs, Tq, nh,
+                        nkv, hd, cap, past, nullptr, NO_PAGES, cos, sin, P, pos, pos_bstride, 8, 8, stream);
+}
+
+extern "C" int oq_kv_append_codes8_ragged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                          void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype,
+                                          int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* lens,
+                                          const float* cos, const float* sin, int64_t P, const int64_t* pos, int64_t pos_bstride,
+                                          void* stream) {
+    OQ_CHECK_ARG(lens, "oq_kv_append_codes8_ragged: null lens");
+    return append_codes("oq_kv_append_codes8_ragged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs,
+                        Tq, nh, nkv, hd, cap, 0, lens, NO_PAGES, cos, sin, P, pos, pos_bstride, 8, 8, stream);
+}
+
+extern "C" int oq_kv_append_codes8_paged(const void* q, const void* k, const void* v, int in_dtype, void* q_out, void* k_out,
+                                         void* v_out, void* k_codes, void* v_codes, float* k_meta, float* v_meta, int dtype,
+                                         int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table, int64_t max_pages,
+                                         int64_t num_pages, int page_size, const int32_t* lens, const float* cos, const float* sin,
+                                         int64_t P, const int64_t* pos, int64_t pos_bstride, void* stream) {
+    OQ_PAGE_MAP("oq_kv_append_codes8_paged");
+    return append_codes("oq_kv_append_codes8_paged", q, k, v, in_dtype, q_out, k_out, v_out, k_codes, v_codes, k_meta, v_meta, dtype, bs,
+                        Tq, nh, nkv, hd, cap, 0, lens, pm, cos, sin, P, pos, pos_bstride, 8, 8, stream);
+}
+
+extern "C" int oq_attn_decode_codes8(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                     const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                     int64_t cap, int64_t L, float scale, const void* mask, int mask_dtype, int64_t mask_bstride,
+                                     int64_t mask_ld, void* workspace, int64_t workspace_bytes, void* stream) {
+    return decode("oq_attn_decode_codes8", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L, nullptr, false,
+                  NO_PAGES, scale, mask, mask_dtype, mask_bstride, mask_ld, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_decode_codes8_ragged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                            const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                            int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                            int64_t workspace_bytes, void* stream) {
+    return decode("oq_attn_decode_codes8_ragged", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+                  lens, true, NO_PAGES, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_decode_codes8_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                           const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                           const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                                           const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    OQ_PAGE_MAP("oq_attn_decode_codes8_paged");
+    return decode("oq_attn_decode_codes8_paged", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
                   lens, true, pm, scale, nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }

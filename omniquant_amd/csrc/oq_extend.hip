@@ -11,8 +11,8 @@
 // K/V tile.  K and V tiles of 64 cached rows go through LDS, double-buffered, in oq_attn.hip's layout and with its S^T operand
 // trick (oq_attn_dev.h); scores, running maximum, row sum and the O accumulator stay in fp32, in the log2 domain.
 // Storage: a ragged slab [bs, nkv, cap, hd] or page pools [num_pages, nkv, PS, hd] found through the page table, each as bf16
-// rows or as 4-bit codes plus (scale, zero-point).  A code row enters LDS as code - zp (small integers, exact in bf16 up to
-// 256); its scale multiplies the score (K) and the probability (V) once per row, which is CodeKV's contract in oq_decode.hip.
+// rows or as 4-bit or 8-bit codes plus (scale, zero-point).  A code row enters LDS as code - zp (small integers, exact in bf16
+// up to 256; an 8-bit row's zp lies in [0, 255]); its scale multiplies the score (K) and the probability (V) once per row, which is CodeKV's contract in oq_decode.hip.
 // Rows no query of the workgroup may see (beyond lens[b] + t of its last row, or with a table entry outside [0, num_pages))
 // are never loaded: they enter LDS as zeros and are masked to -inf, so scratch rows holding NaN cannot reach a result.
 // Launch grid, split plan and workspace depend on shapes and L only.  Partials go to the decode workspace layout and are
@@ -49,7 +49,7 @@ struct ExtP {
     const bf16_t* q;
     bf16_t* o;
     float* ws;
-    const void *k, *v;                  // bf16 rows, or code rows of hd / 2 bytes
+    const void *k, *v;                  // bf16 rows, or code rows of hd / 2 (4-bit) or hd (8-bit) bytes
     const f32x2 *km, *vm;               // (scale, zero-point) per code row
     const int32_t* lens;
     PageMap pm;
@@ -87,24 +87,33 @@ __device__ __forceinline__ bf16x8 frag_tr(const char* lds, int r0, int col0, int
 }
 
 // ---- a thread's share of a key tile on its way from memory to LDS: 64 / NP rows x one 16-byte chunk (8 dims) each.  bf16
-//      rows: the chunk itself; code rows: the chunk's word of 8 codes plus the row's (scale, zero-point), unpacked to code - zp
-//      when it is stored.  The same registers serve K and then V of a tile. ------------------------------------------------
-template <int HD, bool CODES>
+//      rows: the chunk itself; code rows: the chunk's 8 codes (4-bit: one word, 8-bit: two) plus the row's (scale, zero-point),
+//      unpacked to code - zp when it is stored.  The same registers serve K and then V of a tile.  CODES: 0, 4 or 8. ---------
+template <int HD, int CODES>
 struct Staged {
     static constexpr int CPR = HD / 8, RPP = EXT_THREADS / CPR, NP = 64 / RPP;
+    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
     u32x4 r[CODES ? 1 : NP];
-    uint32_t w[CODES ? NP : 1];
+    uint32_t w[CODES == 4 ? NP : 1];
+    u32x2 w8[CODES == 8 ? NP : 1];
     f32x2 mt[CODES ? NP : 1];
 
     // idx[p]: the buffer row of the thread's p-th row, or -1 (not loaded: zeros)
     __device__ __forceinline__ void load(const void* buf, const f32x2* meta, const int64_t (&idx)[NP], int chunk) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            if constexpr (CODES) {
+            if constexpr (CODES == 4) {
                 w[p] = 0u;
                 mt[p] = f32x2{0.f, 0.f};
                 if (idx[p] >= 0) {
                     w[p] = *reinterpret_cast<const uint32_t*>((const uint8_t*)buf + idx[p] * (HD / 2) + chunk * 4);
+                    mt[p] = meta[idx[p]];
+                }
+            } else if constexpr (CODES == 8) {
+                w8[p] = u32x2{0u, 0u};
+                mt[p] = f32x2{0.f, 0.f};
+                if (idx[p] >= 0) {
+                    w8[p] = *reinterpret_cast<const u32x2*>((const uint8_t*)buf + idx[p] * HD + chunk * 8);
                     mt[p] = meta[idx[p]];
                 }
             } else {
@@ -118,14 +127,20 @@ struct Staged {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
             const int row = row0 + RPP * p;
-            if constexpr (CODES) {
-                // dim d of the row in nibble d % 8 of word d / 8: this chunk is one word
-                const uint32_t lo = w[p] & 0x0F0F0F0Fu, hi = (w[p] >> 4) & 0x0F0F0F0Fu;
+            if constexpr (CODES != 0) {
                 bf16x8 x;
+                if constexpr (CODES == 4) {
+                    // dim d of the row in nibble d % 8 of word d / 8: this chunk is one word
+                    const uint32_t lo = w[p] & 0x0F0F0F0Fu, hi = (w[p] >> 4) & 0x0F0F0F0Fu;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    x[2 * i] = (bf16_t)((float)((lo >> (8 * i)) & 0xFFu) - mt[p][1]);
-                    x[2 * i + 1] = (bf16_t)((float)((hi >> (8 * i)) & 0xFFu) - mt[p][1]);
+                    for (int i = 0; i < 4; ++i) {
+                        x[2 * i] = (bf16_t)((float)((lo >> (8 * i)) & 0xFFu) - mt[p][1]);
+                        x[2 * i + 1] = (bf16_t)((float)((hi >> (8 * i)) & 0xFFu) - mt[p][1]);
+                    }
+                } else {
+                    // dim d of the row in byte d: this chunk is two words
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) x[i] = (bf16_t)((float)((w8[p][i >> 2] >> (8 * (i & 3))) & 0xFFu) - mt[p][1]);
                 }
                 if (idx[p] < 0) x = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
                 *reinterpret_cast<bf16x8*>(lds + lds_off<HD>(row, chunk)) = x;
@@ -142,7 +157,7 @@ struct Staged {
 // is masked for the lane's query of block qb iff 16kb + i > dq[qb] (dq = last visible row - first row of the tile - 4g), and,
 // PAGED, when the row was not loaded.  A query row with no visible key yet keeps m = -inf, l = 0, o = 0.
 // meta: the tile's [K scale | V scale | loaded flag] x 64.  MID: called between the S^T MFMAs and the softmax.
-template <int HD, int NQB, bool DIAG, bool CODES, bool PAGED, typename MID>
+template <int HD, int NQB, bool DIAG, int CODES, bool PAGED, typename MID>
 __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const float* meta, const bf16x8 (&qf)[NQB][HD / 32],
                                          f32x4 (&o)[NQB][HD / 16], float (&m)[NQB], float (&l)[NQB], const int (&dq)[NQB],
                                          float zs, int lane, MID&& mid) {
@@ -171,7 +186,7 @@ __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const f
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
         f32x4 f = {zs, zs, zs, zs}, ok = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (CODES) {
+        if constexpr (CODES != 0) {
             const f32x4 skk = *reinterpret_cast<const f32x4*>(meta + 16 * kb + 4 * g);
 #pragma unroll
             for (int i = 0; i < 4; ++i) f[i] = skk[i] * zs;
@@ -216,7 +231,7 @@ __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const f
                 for (int i = 0; i < 4; ++i) o[qb][db][i] *= alpha;
         }
     }
-    if constexpr (CODES) {
+    if constexpr (CODES != 0) {
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
             const f32x4 svk = *reinterpret_cast<const f32x4*>(meta + 64 + 16 * kb + 4 * g);
@@ -241,7 +256,7 @@ __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const f
     }
 }
 
-template <int HD, int NQB, bool CODES, bool PAGED>
+template <int HD, int NQB, int CODES, bool PAGED>
 __global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
     constexpr int TILE = 64 * HD * 2, KS = HD / 32, DB = HD / 16, QT = 64 * NQB;
     using St = Staged<HD, CODES>;
@@ -391,7 +406,7 @@ __global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
     }
 }
 
-template <int HD, int NQB, bool CODES, bool PAGED>
+template <int HD, int NQB, int CODES, bool PAGED>
 void launch_extend(const ExtP& p, int64_t bs, hipStream_t st) {
     hipLaunchKernelGGL((attn_extend_kernel<HD, NQB, CODES, PAGED>), dim3((unsigned)(p.nqt * p.ns), p.nkv, bs), dim3(EXT_THREADS), 0, st, p);
     if (p.ns > 1)
@@ -400,19 +415,22 @@ void launch_extend(const ExtP& p, int64_t bs, hipStream_t st) {
 }
 
 template <int HD, int NQB>
-void launch_extend_kv(bool codes, const ExtP& p, int64_t bs, hipStream_t st) {
-    if (codes) {
-        if (p.pm.table) launch_extend<HD, NQB, true, true>(p, bs, st);
-        else launch_extend<HD, NQB, true, false>(p, bs, st);
+void launch_extend_kv(int codes, const ExtP& p, int64_t bs, hipStream_t st) {
+    if (codes == 8) {
+        if (p.pm.table) launch_extend<HD, NQB, 8, true>(p, bs, st);
+        else launch_extend<HD, NQB, 8, false>(p, bs, st);
+    } else if (codes) {
+        if (p.pm.table) launch_extend<HD, NQB, 4, true>(p, bs, st);
+        else launch_extend<HD, NQB, 4, false>(p, bs, st);
     } else {
-        if (p.pm.table) launch_extend<HD, NQB, false, true>(p, bs, st);
-        else launch_extend<HD, NQB, false, false>(p, bs, st);
+        if (p.pm.table) launch_extend<HD, NQB, 0, true>(p, bs, st);
+        else launch_extend<HD, NQB, 0, false>(p, bs, st);
     }
 }
 
-// codes: k / v are the code buffers of a 4-bit cache and k_meta / v_meta its (scale, zero-point) pairs; else a bf16 cache's
-// buffers.  pm.table: the buffers are page pools and cap = max_pages * page size.
-int extend(const char* fn, bool codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
+// codes (0, 4 or 8): k / v are the code buffers of a cache of that width and k_meta / v_meta its (scale, zero-point) pairs; 0: a
+// bf16 cache's buffers.  pm.table: the buffers are page pools and cap = max_pages * page size.
+int extend(const char* fn, int codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
            int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, const int32_t* lens, const PageMap& pm,
            float scale, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!oq_attn_extend_supported(dtype, Tq, hd)) {
@@ -466,7 +484,7 @@ extern "C" int64_t oq_attn_extend_workspace(int64_t bs, int nh, int nkv, int64_t
 extern "C" int oq_attn_extend(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int64_t bs, int64_t Tq,
                               int nh, int nkv, int hd, int64_t cap, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-    return extend("oq_attn_extend", false, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+    return extend("oq_attn_extend", 0, q, k_cache, v_cache, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
                   NO_PAGES, scale, workspace, workspace_bytes, stream);
 }
 
@@ -474,7 +492,7 @@ extern "C" int oq_attn_extend_codes(const void* q, const void* k_codes, const vo
                                     void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
                                     const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes,
                                     void* stream) {
-    return extend("oq_attn_extend_codes", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+    return extend("oq_attn_extend_codes", 4, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
                   NO_PAGES, scale, workspace, workspace_bytes, stream);
 }
 
@@ -483,7 +501,7 @@ extern "C" int oq_attn_extend_paged(const void* q, const void* k_pool, const voi
                                     int page_size, const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
     OQ_PAGE_MAP("oq_attn_extend_paged");
-    return extend("oq_attn_extend_paged", false, q, k_pool, v_pool, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+    return extend("oq_attn_extend_paged", 0, q, k_pool, v_pool, nullptr, nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
                   pm, scale, workspace, workspace_bytes, stream);
 }
 
@@ -493,6 +511,24 @@ extern "C" int oq_attn_extend_codes_paged(const void* q, const void* k_codes, co
                                           const int32_t* lens, int64_t L_bound, float scale, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
     OQ_PAGE_MAP("oq_attn_extend_codes_paged");
-    return extend("oq_attn_extend_codes_paged", true, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+    return extend("oq_attn_extend_codes_paged", 4, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
+                  lens, pm, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_extend_codes8(const void* q, const void* k_codes, const void* v_codes, const float* k_meta, const float* v_meta,
+                                     void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap,
+                                     const int32_t* lens, int64_t L_bound, float scale, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+    return extend("oq_attn_extend_codes8", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound, lens,
+                  NO_PAGES, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_extend_codes8_paged(const void* q, const void* k_codes, const void* v_codes, const float* k_meta,
+                                           const float* v_meta, void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd,
+                                           const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size,
+                                           const int32_t* lens, int64_t L_bound, float scale, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    OQ_PAGE_MAP("oq_attn_extend_codes8_paged");
+    return extend("oq_attn_extend_codes8_paged", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
                   lens, pm, scale, workspace, workspace_bytes, stream);
 }

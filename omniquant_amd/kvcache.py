@@ -14,6 +14,12 @@ per row.  A stored element's value is fp32((float(code) - zp) * scale) -- bit fo
 holds -- and dequantize() / unpack_codes() are that contract in plain torch.  72 bytes per head row of 128 instead of 256
 (bfloat16) or 512 (float32).
 
+code_bits=8 (weight-only blocks, whose k / v sit on no grid) stores one byte per dim: k_codes / v_codes uint8 [bs, nkv, cap, hd],
+byte d of a row holding dim d, with the same meta and the same value expression.  The appending kernel quantises the post-RoPE
+k and v per (token, head) over hd on the asymmetric 255-level grid, the row range first widened to contain zero (zero-point in
+[0, 255]); an all-zero row is codes 0 under meta (0, 0) and reads back as exact zeros.  136 bytes per head row of 128.  The
+cache's rows ARE the dequantised values: the block's prefill attends them too, so a row has one value wherever it is used.
+
 ragged=True (either kind): every sequence of the batch has its own length.  `lengths` is an int32 [bs] tensor ON THE DEVICE,
 which the append and the attention kernels read themselves (ops.kv_append(..., lengths=), ops.decode_attention(..., lengths=)):
 sequence b's valid rows are [0, lengths[b]), a step needs no padding mask and no position tensor, and nothing about its
@@ -36,11 +42,17 @@ from ._capi import OQError
 _DTYPES = (torch.bfloat16, torch.float32)
 
 
-def unpack_codes(codes, meta):
+def unpack_codes(codes, meta, bits=4):
     """float32 [..., hd] values of code rows uint8 [..., hd // 2] under meta float32 [..., 2] = (scale, zero-point): dim 2i is
     the low nibble of byte i, dim 2i + 1 its high nibble, value = (code - zp) * scale with the subtraction and the multiply in
-    float32.  Pure torch (any device): the value contract of the code cache, as PackedLinear.dequantize() is of the weights."""
-    c = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(*codes.shape[:-1], 2 * codes.shape[-1]).to(torch.float32)
+    float32.  bits=8: code rows uint8 [..., hd], byte d holding dim d, the same expression.
+    Pure torch (any device): the value contract of the code cache, as PackedLinear.dequantize() is of the weights."""
+    if bits == 8:
+        c = codes.to(torch.float32)
+    elif bits == 4:
+        c = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(*codes.shape[:-1], 2 * codes.shape[-1]).to(torch.float32)
+    else:
+        raise OQError(f"unpack_codes: bits {bits} (4 or 8)")
     return (c - meta[..., 1:2]) * meta[..., 0:1]
 
 
@@ -56,9 +68,9 @@ class PackedKVCache:
         if min(int(bs), int(nkv), int(hd)) <= 0 or int(capacity) < 0:
             raise OQError(f"PackedKVCache: bs {bs}, nkv {nkv}, hd {hd}, capacity {capacity}")
         self.bs, self.nkv, self.hd, self.dtype, self.device = int(bs), int(nkv), int(hd), dtype, device
-        if code_bits is not None and code_bits != 4:
-            raise OQError(f"PackedKVCache: code_bits {code_bits} (None: float rows, or 4)")
-        if code_bits == 4 and self.hd not in (64, 128):
+        if code_bits is not None and code_bits not in (4, 8):
+            raise OQError(f"PackedKVCache: code_bits {code_bits} (None: float rows, 4 or 8)")
+        if code_bits is not None and self.hd not in (64, 128):
             raise OQError(f"PackedKVCache: a code cache covers head_dim 64 and 128, not {self.hd}")
         self.code_bits = code_bits
         self.length = 0
@@ -77,7 +89,7 @@ class PackedKVCache:
             if self.code_bits is None:
                 t = torch.empty(shape + (self.hd,), dtype=self.dtype, device=self.device)
             elif name.endswith("codes"):
-                t = torch.empty(shape + (self.hd // 2,), dtype=torch.uint8, device=self.device)
+                t = torch.empty(shape + (self.hd * self.code_bits // 8,), dtype=torch.uint8, device=self.device)
             else:
                 t = torch.empty(shape + (2,), dtype=torch.float32, device=self.device)
             if keep is not None and keep.length:
@@ -135,7 +147,7 @@ class PackedKVCache:
         n = min(max(int(self.lengths[b]), 0), self.capacity)
         if self.code_bits is None:
             return self.k[b, :, :n].clone(), self.v[b, :, :n].clone()
-        return tuple(unpack_codes(c[b, :, :n], m[b, :, :n]).to(self.dtype)
+        return tuple(unpack_codes(c[b, :, :n], m[b, :, :n], self.code_bits).to(self.dtype)
                      for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
 
     def dequantize(self):
@@ -145,7 +157,7 @@ class PackedKVCache:
         if self.code_bits is None:
             return self.k[:, :, :self.length], self.v[:, :, :self.length]
         n = self.length
-        return tuple(unpack_codes(c[:, :, :n], m[:, :, :n]).to(self.dtype)
+        return tuple(unpack_codes(c[:, :, :n], m[:, :, :n], self.code_bits).to(self.dtype)
                      for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
 
     def reserve(self, n):
@@ -190,6 +202,8 @@ class PackedKVCache:
         the tensors passed in are never modified.  head_bits (W4A4 blocks): the rows are quantised per (token, head) over hd on
         that grid as they are imported (ops.kv_append_quant without rotation), which is what the block's own appends store.
         code_bits=4 (with head_bits=4): the same quantisation, once, into a code cache.
+        code_bits=8 (head_bits must be None: the weight-only blocks): the raw rows pass the 8-bit code cache's own quantiser
+        (ops.kv_append_codes without rotation), once.
         ragged: refused -- a tuple has one length for the whole batch."""
         if ragged:
             raise OQError("past_key_value: a (k, v) tuple has one length for the batch and cannot fill a ragged cache")
@@ -201,10 +215,18 @@ class PackedKVCache:
         if not (k.is_cuda and v.is_cuda):
             raise OQError("past_key_value: GPU tensors expected (no CPU fallback)")
         bs, nkv, T, hd = k.shape
-        if code_bits is not None and head_bits != code_bits:
+        if code_bits == 8:
+            if head_bits is not None:
+                raise OQError(f"past_key_value: an 8-bit code cache holds a weight-only block's rows (head_bits {head_bits} given)")
+        elif code_bits is not None and head_bits != code_bits:
             raise OQError(f"past_key_value: a {code_bits}-bit code cache holds rows quantised on that grid (head_bits {head_bits})")
         c = cls(bs, nkv, hd, dtype or k.dtype, k.device, max(int(capacity or 0), T), code_bits=code_bits)
-        if T and head_bits is not None:
+        if T and code_bits == 8:
+            from . import ops
+            src = c.dtype if k.dtype == c.dtype else torch.float32
+            kt, vt = (t.transpose(1, 2).to(src).contiguous() for t in (k, v))         # [bs, T, nkv, hd], fresh copies
+            ops.kv_append_codes(kt, vt, c.dtype, c.k_codes, c.v_codes, c.k_meta, c.v_meta, past=0)
+        elif T and head_bits is not None:
             from . import ops
             src = c.dtype if k.dtype == c.dtype else torch.float32
             kt, vt = (t.transpose(1, 2).to(src).contiguous() for t in (k, v))         # [bs, T, nkv, hd], fresh copies
@@ -297,8 +319,8 @@ class PageAllocator:
 
 
 class PagedKVCache:
-    """One layer's paged, ragged KV cache.  Pools k / v [num_pages, nkv, page_size, hd] in `dtype` -- or, with code_bits=4,
-    k_codes / v_codes uint8 [num_pages, nkv, page_size, hd // 2] and k_meta / v_meta float32 [num_pages, nkv, page_size, 2] --
+    """One layer's paged, ragged KV cache.  Pools k / v [num_pages, nkv, page_size, hd] in `dtype` -- or, with code_bits=4 / 8,
+    k_codes / v_codes uint8 [num_pages, nkv, page_size, hd // 2 resp. hd] and k_meta / v_meta float32 [num_pages, nkv, page_size, 2] --
     and page_table int32 [bs, max_pages] on the device: logical row j of sequence b lives in page page_table[b, j // page_size]
     (entries of pages a sequence does not hold are -1, which the kernels neither store to nor load).  `lengths` (device) and
     `length` (host upper bound) are a ragged PackedKVCache's; capacity = max_pages * page_size rows per sequence.
@@ -330,8 +352,8 @@ class PagedKVCache:
             raise OQError(f"PagedKVCache: page_size {page_size} (16, 32, 64 or 128)")
         if int(hd) not in (64, 128):
             raise OQError(f"PagedKVCache: head_dim {hd} (the decode kernels cover 64 and 128)")
-        if code_bits is not None and code_bits != 4:
-            raise OQError(f"PagedKVCache: code_bits {code_bits} (None: float rows, or 4)")
+        if code_bits is not None and code_bits not in (4, 8):
+            raise OQError(f"PagedKVCache: code_bits {code_bits} (None: float rows, 4 or 8)")
         self.bs, self.nkv, self.hd, self.dtype, self.device = int(bs), int(nkv), int(hd), dtype, device
         self.num_pages, self.page_size, self.max_pages, self.code_bits = int(num_pages), int(page_size), int(max_pages), code_bits
         self.length = 0
@@ -346,7 +368,7 @@ class PagedKVCache:
             if code_bits is None:
                 t = torch.empty(shape + (self.hd,), dtype=dtype, device=device)
             elif name.endswith("codes"):
-                t = torch.empty(shape + (self.hd // 2,), dtype=torch.uint8, device=device)
+                t = torch.empty(shape + (self.hd * code_bits // 8,), dtype=torch.uint8, device=device)
             else:
                 t = torch.empty(shape + (2,), dtype=torch.float32, device=device)
             setattr(self, name, t)
@@ -522,7 +544,7 @@ class PagedKVCache:
             return t[idx].transpose(0, 1).reshape(self.nkv, -1, t.shape[3])[:, :n]
         if self.code_bits is None:
             return rows(self.k).clone(), rows(self.v).clone()
-        return tuple(unpack_codes(rows(c), rows(m)).to(self.dtype)
+        return tuple(unpack_codes(rows(c), rows(m), self.code_bits).to(self.dtype)
                      for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
 
     # ---- the (k, v) tuple surface: refused, as for every ragged cache ------------------------------------------------------------

@@ -1750,14 +1750,22 @@ def _kv_quant_outs(fn, q, k, v, out_dtype, q_out, k_out, v_out):
     return q, k.contiguous(), v.contiguous()
 
 
-def _code_buffers(fn, k_codes, v_codes, k_meta, v_meta, bs, nkv, hd):
-    """Validate the four buffers of a 4-bit code cache (kvcache.PackedKVCache(code_bits=4)); returns the capacity."""
+def _code_bits(k_codes, hd):
+    """The width of a code cache's codes from its buffers: rows of hd bytes are 8-bit codes, everything else counts as 4-bit
+    (rows of hd // 2 bytes; _code_buffers / _page_pool then check the shape for the width)."""
+    return 8 if torch.is_tensor(k_codes) and k_codes.dim() == 4 and k_codes.shape[3] == hd else 4
+
+
+def _code_buffers(fn, k_codes, v_codes, k_meta, v_meta, bs, nkv, hd, bits=4):
+    """Validate the four buffers of a code cache of `bits` (kvcache.PackedKVCache(code_bits=4 | 8)): code rows of hd // 2 resp.
+    hd bytes; returns the capacity."""
     if hd not in (64, 128):
         raise C.OQError(f"{fn}: head_dim {hd} (a code cache covers 64 and 128)")
-    if k_codes.dim() != 4 or (k_codes.shape[0], k_codes.shape[1], k_codes.shape[3]) != (bs, nkv, hd // 2):
-        raise C.OQError(f"{fn}: codes {tuple(k_codes.shape)} (expected [{bs}, {nkv}, cap, {hd // 2}])")
+    row = hd if bits == 8 else hd // 2
+    if k_codes.dim() != 4 or (k_codes.shape[0], k_codes.shape[1], k_codes.shape[3]) != (bs, nkv, row):
+        raise C.OQError(f"{fn}: codes {tuple(k_codes.shape)} (expected [{bs}, {nkv}, cap, {row}])")
     cap = k_codes.shape[2]
-    for t, tail, dtype in ((k_codes, hd // 2, torch.uint8), (v_codes, hd // 2, torch.uint8), (k_meta, 2, torch.float32),
+    for t, tail, dtype in ((k_codes, row, torch.uint8), (v_codes, row, torch.uint8), (k_meta, 2, torch.float32),
                            (v_meta, 2, torch.float32)):
         if tuple(t.shape) != (bs, nkv, cap, tail) or t.dtype != dtype:
             raise C.OQError(f"{fn}: code-cache buffer {tuple(t.shape)} {t.dtype} (expected {(bs, nkv, cap, tail)} {dtype})")
@@ -1771,12 +1779,21 @@ def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q
     v_meta (float32 [bs, nkv, cap, 2]) its (scale, zero-point); (code - zp) * scale is, bit for bit, what kv_append_quant
     writes to a float32 cache.  q_out / k_out / v_out receive the fake-quant values in out_dtype as they do there.
     lengths: as in kv_append (oq_kv_append_quant_codes_ragged).  page_table: as in kv_append, the four buffers being page pools
-    [num_pages, nkv, PS, hd // 2 | 2] (oq_kv_append_quant_codes_paged)."""
+    [num_pages, nkv, PS, hd // 2 | 2] (oq_kv_append_quant_codes_paged).
+    Code rows of hd bytes (k_codes [..., hd]: the 8-bit code cache of the weight-only blocks) select oq_kv_append_codes8 and
+    its _ragged / _paged forms: k and v alone are quantised, on the 255-level grid whose row range contains zero (an all-zero
+    row: codes 0, meta (0, 0), exact zeros); q_out receives the rotated q's values as kv_append gives them, and k_out / v_out
+    the dequantised values (code - zp) * scale rounded once to out_dtype."""
     bs, Tq, nkv, hd = k.shape
+    bits = _code_bits(k_codes, hd)
+    row = hd if bits == 8 else hd // 2
+    names = ("oq_kv_append_codes8_paged", "oq_kv_append_codes8_ragged", "oq_kv_append_codes8") if bits == 8 else \
+        ("oq_kv_append_quant_codes_paged", "oq_kv_append_quant_codes_ragged", "oq_kv_append_quant_codes")
+    width = () if bits == 8 else (4,)           # the 4-bit entry points take nbits
     pages = None
     if page_table is not None:
         pages = _page_pool("kv_append_codes", page_table, lengths, past, None, bs, nkv,
-                           ((k_codes, hd // 2, torch.uint8), (v_codes, hd // 2, torch.uint8), (k_meta, 2, torch.float32),
+                           ((k_codes, row, torch.uint8), (v_codes, row, torch.uint8), (k_meta, 2, torch.float32),
                             (v_meta, 2, torch.float32)))
         if hd not in (64, 128):
             raise C.OQError(f"kv_append_codes: head_dim {hd} (a code cache covers 64 and 128)")
@@ -1785,7 +1802,7 @@ def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q
     if tuple(v.shape) != tuple(k.shape) or v.dtype != k.dtype or k.dtype not in (torch.float32, out_dtype):
         raise C.OQError(f"kv_append_codes: k {tuple(k.shape)} {k.dtype} / v {tuple(v.shape)} {v.dtype} (float32 or {out_dtype})")
     _, nh, P, pbs, positions = _kv_append_args("kv_append_codes", k, v, None, None, out_dtype, past, q, cos, sin, positions)
-    cap = 0 if pages else _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd)
+    cap = 0 if pages else _code_buffers("kv_append_codes", k_codes, v_codes, k_meta, v_meta, bs, nkv, hd, bits)
     ragged = lengths is not None
     if not ragged and (past < 0 or past + Tq > cap):
         raise C.OQError(f"kv_append_codes: rows [{past}, {past + Tq}) beyond the capacity {cap}")
@@ -1793,13 +1810,13 @@ def kv_append_codes(k, v, out_dtype, k_codes, v_codes, k_meta, v_meta, past=0, q
         raise C.OQError("kv_append_codes: k_out and v_out go together")
     q, k, v = _kv_quant_outs("kv_append_codes", q, k, v, out_dtype, q_out, k_out, v_out)
     if pages:
-        C.call("oq_kv_append_quant_codes_paged", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
+        C.call(names[0], C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k), C.ptr(q_out), C.ptr(k_out), C.ptr(v_out),
                C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype], bs, Tq, nh, nkv, hd, C.ptr(pages[0]),
-               *pages[1:], C.ptr(lengths), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4, C.stream())
+               *pages[1:], C.ptr(lengths), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, *width, C.stream())
         return q_out
-    C.call("oq_kv_append_quant_codes_ragged" if ragged else "oq_kv_append_quant_codes", C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k),
+    C.call(names[1] if ragged else names[2], C.ptr(q), C.ptr(k), C.ptr(v), C.dt(k),
            C.ptr(q_out), C.ptr(k_out), C.ptr(v_out), C.ptr(k_codes), C.ptr(v_codes), C.fptr(k_meta), C.fptr(v_meta), C._DT[out_dtype],
-           bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, 4,
+           bs, Tq, nh, nkv, hd, cap, C.ptr(lengths) if ragged else int(past), C.fptr(cos), C.fptr(sin), P, C.ptr(positions), pbs, *width,
            C.stream())
     return q_out
 
@@ -1881,9 +1898,13 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
     code_bits 4 or the (k_codes, v_codes, k_meta, v_meta) buffers; K and V are dequantised in registers as (code - zp) * scale.
     Same scores, softmax, mask handling, split plan and reproducibility as decode_attention; q and o in the compute dtype.
     lengths: as in decode_attention (oq_attn_decode_codes_ragged).  page_table: as in decode_attention, `cache` being a
-    PagedKVCache's four page pools or the cache itself (oq_attn_decode_codes_paged)."""
+    PagedKVCache's four page pools or the cache itself (oq_attn_decode_codes_paged).
+    An 8-bit code cache (code_bits 8, or buffers whose code rows have hd bytes) runs oq_attn_decode_codes8 and its _ragged /
+    _paged forms: the same loops and sums on byte codes."""
     bs, Tq, nh, hd = q.shape
     bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
+    bits = _code_bits(bufs[0], hd) if isinstance(cache, (tuple, list)) else cache.code_bits
+    row, sfx = (hd, "codes8") if bits == 8 else (hd // 2, "codes")
     pages = None
     if page_table is not None:
         if len(bufs) != 4 or not torch.is_tensor(bufs[0]) or bufs[0].dim() != 4:
@@ -1892,14 +1913,14 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
             raise C.OQError(f"decode_attention_codes: head_dim {hd} (a code cache covers 64 and 128)")
         nkv = bufs[0].shape[1]
         pages = _page_pool("decode_attention_codes", page_table, lengths, 0, mask, bs, nkv,
-                           ((bufs[0], hd // 2, torch.uint8), (bufs[1], hd // 2, torch.uint8), (bufs[2], 2, torch.float32),
+                           ((bufs[0], row, torch.uint8), (bufs[1], row, torch.uint8), (bufs[2], 2, torch.float32),
                             (bufs[3], 2, torch.float32)))
         cap = pages[1] * pages[3]
     else:
         if len(bufs) != 4 or bufs[0].dim() != 4 or bufs[0].shape[0] != bs:
             raise C.OQError(f"decode_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
         nkv = bufs[0].shape[1]
-        cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd)
+        cap = _code_buffers("decode_attention_codes", *bufs, bs, nkv, hd, bits)
     if lengths is not None:
         lengths = _ragged_decode_args("decode_attention_codes", lengths, bs, bufs[0].device, mask, Tq, L, cap)
     if q.dtype not in (torch.float32, torch.bfloat16):
@@ -1911,16 +1932,16 @@ def decode_attention_codes(q, cache, L, scale, mask=None, out=None, workspace=No
         workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=q.device)
     o = torch.empty_like(q) if out is None else out
     if pages:
-        C.call("oq_attn_decode_codes_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+        C.call(f"oq_attn_decode_{sfx}_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
                C.dt(q), bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
                workspace.numel() * workspace.element_size(), C.stream())
         return o
     if lengths is not None:
-        C.call("oq_attn_decode_codes_ragged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+        C.call(f"oq_attn_decode_{sfx}_ragged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
                C.dt(q), bs, Tq, nh, nkv, hd, cap, C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
                workspace.numel() * workspace.element_size(), C.stream())
         return o
-    C.call("oq_attn_decode_codes", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
+    C.call(f"oq_attn_decode_{sfx}", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
            bs, Tq, nh, nkv, hd, cap, int(L), float(scale), mptr, mdt, mbs, mld, C.ptr(workspace),
            workspace.numel() * workspace.element_size(), C.stream())
     return o
@@ -2027,9 +2048,12 @@ def extend_attention_codes(q, cache, L, scale, lengths, page_table=None, out=Non
     """extend_attention over a 4-bit code cache (oq_attn_extend_codes): `cache` is a cache with code_bits 4 or its (k_codes,
     v_codes, k_meta, v_meta) buffers.  A row enters the MFMA as code - zero_point; its scale multiplies the score (K) and the
     probability (V) once per row, as in decode_attention_codes.  page_table: the buffers are page pools
-    (oq_attn_extend_codes_paged)."""
+    (oq_attn_extend_codes_paged).  An 8-bit code cache (code_bits 8, or code rows of hd bytes) runs oq_attn_extend_codes8 /
+    _paged: its zero-points lie in [0, 255], so code - zero_point stays exact in bfloat16."""
     bs, Tq, nh, hd = q.shape
     bufs = cache if isinstance(cache, (tuple, list)) else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
+    bits = _code_bits(bufs[0], hd) if isinstance(cache, (tuple, list)) else cache.code_bits
+    row, sfx = (hd, "codes8") if bits == 8 else (hd // 2, "codes")
     if len(bufs) != 4 or not torch.is_tensor(bufs[0]) or bufs[0].dim() != 4:
         raise C.OQError("extend_attention_codes: (k_codes, v_codes, k_meta, v_meta) buffers or page pools expected")
     nkv = bufs[0].shape[1]
@@ -2038,21 +2062,21 @@ def extend_attention_codes(q, cache, L, scale, lengths, page_table=None, out=Non
         if hd not in (64, 128):
             raise C.OQError(f"extend_attention_codes: head_dim {hd} (a code cache covers 64 and 128)")
         pages = _page_pool("extend_attention_codes", page_table, lengths, 0, None, bs, nkv,
-                           ((bufs[0], hd // 2, torch.uint8), (bufs[1], hd // 2, torch.uint8), (bufs[2], 2, torch.float32),
+                           ((bufs[0], row, torch.uint8), (bufs[1], row, torch.uint8), (bufs[2], 2, torch.float32),
                             (bufs[3], 2, torch.float32)))
         cap = pages[1] * pages[3]
     else:
         if bufs[0].shape[0] != bs:
             raise C.OQError(f"extend_attention_codes: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
-        cap = _code_buffers("extend_attention_codes", *bufs, bs, nkv, hd)
+        cap = _code_buffers("extend_attention_codes", *bufs, bs, nkv, hd, bits)
     q, lengths, o, workspace, ws_n = _extend_args("extend_attention_codes", q, lengths, bs, bufs[0].device, Tq, L, cap, nh, nkv, out,
                                                   workspace)
     if pages:
-        C.call("oq_attn_extend_codes_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
+        C.call(f"oq_attn_extend_{sfx}_paged", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o),
                C.dt(q), bs, Tq, nh, nkv, hd, C.ptr(pages[0]), *pages[1:], C.ptr(lengths), int(L), float(scale), C.ptr(workspace),
                ws_n, C.stream())
         return o
-    C.call("oq_attn_extend_codes", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
+    C.call(f"oq_attn_extend_{sfx}", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), C.fptr(bufs[2]), C.fptr(bufs[3]), C.ptr(o), C.dt(q),
            bs, Tq, nh, nkv, hd, cap, C.ptr(lengths), int(L), float(scale), C.ptr(workspace), ws_n, C.stream())
     return o
 

@@ -277,15 +277,20 @@ def _replace_module(root, name, new):
 
 def _mark_packed(qlayer, act_bits, act_quant=False, kv_cache_bits=None):
     """The block's forward checks this once at entry and takes the packed inference path (block_common.packed_guard).
-    kv_cache_bits (None or 4): the storage kind of the KV caches the block creates (kvcache.PackedKVCache code_bits)."""
+    kv_cache_bits (None, 4 or 8): the storage kind of the KV caches the block creates (kvcache.PackedKVCache code_bits)."""
     qlayer._oq_packed = {"act_bits": int(act_bits), "act_quant": bool(act_quant), "kv_cache_bits": kv_cache_bits}
 
 
 def _check_kv_cache_bits(kv_cache_bits, act_quant):
     if kv_cache_bits is None:
         return
+    if kv_cache_bits == 8:
+        if act_quant:
+            raise C.OQError("kv_cache_bits=8 is the weight-only blocks' code cache; an act_quant=True (W4A4) block's k / v sit on "
+                            "its 4-bit head grid (kv_cache_bits=4)")
+        return
     if kv_cache_bits != 4:
-        raise C.OQError(f"kv_cache_bits {kv_cache_bits} (None: float rows, or 4)")
+        raise C.OQError(f"kv_cache_bits {kv_cache_bits} (None: float rows, 4 with act_quant=True, or 8 without)")
     if not act_quant:
         raise C.OQError("kv_cache_bits=4 needs act_quant=True: a weight-only block's k / v are not on a 4-bit grid, and quantising "
                         "them for the cache would change the model")
@@ -353,7 +358,9 @@ def pack_block(qlayer, wbits, act_quant=False, kv_cache_bits=None):
     check_act_quant_eligible): the same buffers -- the state_dict is the weight-only pack's -- with act_bits 4 linears, and
     the forward runs the integer path (llama_block.QuantLlamaDecoderLayer._packed_forward_a4).  kv_cache_bits=4 (with
     act_quant=True): the block's KV caches store the head quantisers' 4-bit codes (kvcache.PackedKVCache code_bits); the values
-    the attention reads are the same."""
+    the attention reads are the same.  kv_cache_bits=8 (weight-only blocks, LLaMA and OPT): the block's KV caches store 8-bit
+    per-(token, head) codes of k / v (PackedKVCache code_bits=8) and every attention, the prefill's included, reads the
+    dequantised rows: a lossy cache, 136 instead of 256 / 512 bytes per head row of 128."""
     from .linear import QuantLinear
     _check_kv_cache_bits(kv_cache_bits, act_quant)
     act_bits = _act_bits(qlayer)

@@ -16,6 +16,11 @@
    and maximum of each kernel, the bf16 kernel's own run-to-run spread (max - min over its median) and the ratio of the
    medians.
 
+   `--codes8`: the `--codes` run with oq_attn_decode_codes8 on an 8-bit code cache (136 bytes per head row of 128) as a third
+   interleaved contestant, at the 7B shape, bs 8, L 8192 and 32768.  A row adds the 8-bit kernel's median / min / max, its
+   ratio to the bf16 kernel of the same run and `codes8_faster_beyond_spread`: whether its median beats the bf16 kernel's by
+   more than the bf16 kernel's own run-to-run spread.
+
 4. `--ragged`: instead of 1 and 2, a batch of 8 sequences of lengths 128 ... 8192 (geometric) at the 7B shape, Tq = 1, on a
    bf16 cache and on a 4-bit code cache: oq_attn_decode_ragged / oq_attn_decode_codes_ragged (per-sequence lengths on the
    device, bound 8192, no mask) against oq_attn_decode / oq_attn_decode_codes on the same batch left-padded to 8192 with a
@@ -42,7 +47,7 @@
    above every Tq that has one.  FLOPs are not reported here: a share of the MFMA peak wants a counter run of its own.
 
 usage: python tools/microbench_decode.py [--out FILE] [--reps 3] [--quick] [--step-only --steps N]
-                                         [--codes | --ragged | --paged | --extend [--rounds 7]]
+                                         [--codes | --codes8 | --ragged | --paged | --extend [--rounds 7]]
 """
 import argparse
 import json
@@ -155,12 +160,14 @@ def kernel_rows(reps, quick, dev):
     return rows
 
 
-def codes_rows(reps, rounds, quick, dev):
+def codes_rows(reps, rounds, quick, dev, codes8=False):
     rows = []
     for name, nh, nkv, hd in SHAPES:
         for bs in BS:
             for L in LS:
                 if quick and (bs != 1 or L not in (2048, 8192)):
+                    continue
+                if codes8 and (name != "7b" or bs != 8 or L not in (8192, 32768)):
                     continue
                 kv_bytes = 2 * bs * nkv * L * hd * 2
                 code_bytes = 2 * bs * nkv * L * (hd // 2 + 8)
@@ -180,9 +187,22 @@ def codes_rows(reps, rounds, quick, dev):
                 csets = [(torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev),
                           torch.randint(0, 256, (bs, nkv, L, hd // 2), dtype=torch.uint8, device=dev), meta(), meta())
                          for _ in range(max(2, -(-COLD_BYTES // code_bytes)))]
-                us, med = interleaved(
-                    ([(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)) for s in fsets],
-                     [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in csets]), reps, rounds)
+                lists = [[(lambda s=s: ops.decode_attention(q, s[0], s[1], L, scale, out=o, workspace=ws)) for s in fsets],
+                         [(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in csets]]
+                if codes8:
+                    code8_bytes = 2 * bs * nkv * L * (hd + 8)
+
+                    def meta8():     # scales and zero-points of a 255-level grid whose range contains zero
+                        m = torch.empty(bs, nkv, L, 2, device=dev)
+                        m[..., 0] = torch.rand(bs, nkv, L, device=dev) * 0.01 + 0.02
+                        m[..., 1] = torch.randint(96, 160, (bs, nkv, L), device=dev).float()
+                        return m
+
+                    c8sets = [(torch.randint(0, 256, (bs, nkv, L, hd), dtype=torch.uint8, device=dev),
+                               torch.randint(0, 256, (bs, nkv, L, hd), dtype=torch.uint8, device=dev), meta8(), meta8())
+                              for _ in range(max(2, -(-COLD_BYTES // code8_bytes)))]
+                    lists.append([(lambda s=s: ops.decode_attention_codes(q, s, L, scale, out=o, workspace=ws)) for s in c8sets])
+                us, med = interleaved(lists, reps, rounds)
                 r = dict(shape=name, nh=nh, nkv=nkv, hd=hd, bs=bs, L=L, Tq=1, dtype="bfloat16", cache="cold", rounds=rounds,
                          bf16_sets=len(fsets), code_sets=len(csets),
                          bf16_us=med[0], bf16_us_min=min(us[0]), bf16_us_max=max(us[0]),
@@ -191,6 +211,12 @@ def codes_rows(reps, rounds, quick, dev):
                          codes_spread=(max(us[1]) - min(us[1])) / med[1],
                          codes_over_bf16=med[1] / med[0], bf16_GBps=kv_bytes / med[0] / 1e3, codes_GBps=code_bytes / med[1] / 1e3,
                          codes_frac_hbm=code_bytes / med[1] * 1e6 / HBM_BPS)
+                if codes8:
+                    r.update(code8_sets=len(c8sets), codes8_us=med[2], codes8_us_min=min(us[2]), codes8_us_max=max(us[2]),
+                             codes8_spread=(max(us[2]) - min(us[2])) / med[2], codes8_over_bf16=med[2] / med[0],
+                             codes8_GBps=code8_bytes / med[2] / 1e3, codes8_frac_hbm=code8_bytes / med[2] * 1e6 / HBM_BPS,
+                             codes8_faster_beyond_spread=bool(med[0] - med[2] > max(us[0]) - min(us[0])))
+                    del c8sets
                 rows.append(r)
                 print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
                 del fsets, csets
@@ -517,6 +543,7 @@ def main():
     ap.add_argument("--step-only", action="store_true", help="only N eager decode steps of the 7B block (for rocprofv3)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--codes", action="store_true", help="the code-cache kernel interleaved with the bf16-cache kernel")
+    ap.add_argument("--codes8", action="store_true", help="--codes with the 8-bit code-cache kernel as a third contestant (7B, bs 8)")
     ap.add_argument("--ragged", action="store_true", help="ragged-batch kernels interleaved with the padded, masked ones")
     ap.add_argument("--paged", action="store_true", help="paged kernels interleaved with the ragged contiguous ones")
     ap.add_argument("--extend", action="store_true", help="the MFMA chunked-prefill kernel interleaved with the ragged decode kernel")
@@ -535,8 +562,8 @@ def main():
         rows = paged_rows(a.reps, a.rounds, a.quick, dev)
     elif a.ragged:
         rows = ragged_rows(a.reps, a.rounds, dev)
-    elif a.codes:
-        rows = codes_rows(a.reps, a.rounds, a.quick, dev)
+    elif a.codes or a.codes8:
+        rows = codes_rows(a.reps, a.rounds, a.quick, dev, codes8=a.codes8)
     else:
         rows = kernel_rows(a.reps, a.quick, dev)
         rows.append(block_step(dev, a.reps))
