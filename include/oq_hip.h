@@ -524,6 +524,26 @@ int oq_attn_extend_codes8_paged(const void* q, const void* k_codes, const void* 
                                 void* o, int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, const int32_t* table,
                                 int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
                                 float scale, void* workspace, int64_t workspace_bytes, void* stream);
+/*   Page moves of a model-wide pool (csrc/oq_kvpool.hip; kvcache.PagedKVPool).  Serving storage has no counterpart in the
+ *      reference, as the paged entry points above have none.  A buffer kind of the pool is [layers, num_pages, ...]: a page is
+ *      one contiguous chunk of page_bytes per layer, layers are layer_stride_bytes apart, and `pool` points at the first layer of
+ *      the range moved.  Page ids are int32 on the device and the host never reads them; an id outside [0, num_pages) is skipped:
+ *      nothing is loaded, and dst resp. the pool keeps its bytes there.  page_bytes > 0 and page_bytes % 16 == 0 (every pool
+ *      shape of the caches qualifies: the smallest page is a meta page of nkv * 16 * 8 bytes), layer_stride_bytes % 16 == 0 and,
+ *      for layers > 1, >= num_pages * page_bytes; pool and dst / src 16-byte aligned.  Anything else, a null pointer with n > 0
+ *      or a negative size returns OQ_E_ARG with nothing launched; n == 0 or layers == 0 launches nothing and succeeds.
+ *   oq_kv_pages_gather: dst [layers][n][page_bytes] (contiguous) receives page page_ids[i] of every layer; ids may repeat.
+ *   oq_kv_pages_scatter: the reverse, from src [layers][n][page_bytes]; the valid ids must be distinct.
+ *   oq_kv_pages_copy: page dst_ids[i] becomes a copy of page src_ids[i] in every layer; a pair with src == dst, or with either id
+ *      outside the pool, is skipped.  The valid dst ids must be distinct and none of them a src id of another pair.
+ *   One launch each: pure 16-byte vector copies, consecutive lanes on consecutive 16 bytes of one page, the grid capped at 2048
+ *      workgroups that stride over (layer, page, slice). */
+int oq_kv_pages_gather(const void* pool, int64_t num_pages, int64_t page_bytes, int64_t layer_stride_bytes, int64_t layers,
+                       const int32_t* page_ids, int64_t n, void* dst, void* stream);
+int oq_kv_pages_scatter(const void* src, void* pool, int64_t num_pages, int64_t page_bytes, int64_t layer_stride_bytes,
+                        int64_t layers, const int32_t* page_ids, int64_t n, void* stream);
+int oq_kv_pages_copy(void* pool, int64_t num_pages, int64_t page_bytes, int64_t layer_stride_bytes, int64_t layers,
+                     const int32_t* src_ids, const int32_t* dst_ids, int64_t n, void* stream);
 
 /* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using

@@ -125,6 +125,10 @@ SIGNATURES = {
     "oq_attn_extend_codes8": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _f32, _vp, _i64, _vp],
     "oq_attn_extend_codes8_paged": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp,
                                     _i64, _f32, _vp, _i64, _vp],
+    # page moves of the model-wide pool (kvcache.PagedKVPool): gather to / scatter from a contiguous buffer, copy inside the pool
+    "oq_kv_pages_gather": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
+    "oq_kv_pages_scatter": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
+    "oq_kv_pages_copy": [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,

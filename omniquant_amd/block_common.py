@@ -74,18 +74,20 @@ class QuantBlockMixin:
         blocks, whose cache holds head-quantised k / v): the tuple's raw rows are quantised once, on import.
         A block packed with kv_cache_bits=4 creates, and converts tuples into, 4-bit code caches; a caller's PackedKVCache of
         either kind is taken as it is (an empty pre-sized code cache switches an unmarked W4A4 block to codes), except that a
-        code cache needs the head quantisers (head_bits 4).  So is a caller's PagedKVCache (paged, ragged storage); a block never
-        creates one by itself.
+        code cache needs the head quantisers (head_bits 4).  So is a caller's PagedKVCache (paged, ragged storage), which a
+        layer view of a model-wide PagedKVPool (pool.layer(l)) is too; a block never creates one by itself.
         A weight-only block (head_bits None) packed with kv_cache_bits=8 creates, and converts tuples into, 8-bit code caches,
         and takes a caller's 8-bit code cache whether marked or not; a W4A4 block refuses one, as a weight-only block refuses
         a 4-bit one."""
         from ._capi import OQError
-        from .kvcache import PackedKVCache, PagedKVCache
+        from .kvcache import PackedKVCache, PagedKVCache, PagedKVPool
         if hd not in (64, 128):
             raise OQError(f"KV-cache decoding covers head_dim 64 and 128 (oq_attn_decode), not {hd}")
         code_bits = self.__dict__["_oq_packed"].get("kv_cache_bits")
         if past_key_value is None:
             return PackedKVCache(bsz, nkv, hd, x.dtype, x.device, Tq, code_bits=code_bits)
+        if isinstance(past_key_value, PagedKVPool):
+            raise OQError(f"{past_key_value!r} holds every layer's pages: pass pool.layer(l) to layer l as past_key_value")
         if isinstance(past_key_value, (PackedKVCache, PagedKVCache)):
             c = past_key_value
             if (c.bs, c.nkv, c.hd) != (bsz, nkv, hd) or c.dtype != x.dtype or c.device != x.device:
@@ -174,7 +176,9 @@ class QuantBlockMixin:
         the same lengths, L and pad-row contract, the same absence of host reads.
         A paged cache (cache.paged, always ragged; kvcache.PagedKVCache): the same ops calls on its page pools with
         page_table=cache.page_table; reserve() gives every sequence the pages the step's rows need (uploading the table only
-        if one was added) and advance() books the step in the cache's host bounds.  Nothing else about the step changes."""
+        if one was added).  Nothing else about the step changes.
+        After the attention a ragged cache books the step itself (cache.book_step): lengths, the bound `length` and, paged, the
+        host bounds; a layer view of a PagedKVPool books it with its pool, which applies it once all layers have."""
         from . import ops
         from ._capi import OQError
         bsz, Tq = q.shape[0], q.shape[1]
@@ -231,11 +235,7 @@ class QuantBlockMixin:
             attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask, lengths=lens, **paged)
         if lens is not None:
             # (after the attention, which reads the pre-step lengths; the stream orders the launches)
-            counts, grow, host_counts = new_tokens
-            lens.add_(Tq if counts is None else counts)
-            cache.length = past + (Tq if grow is None else grow)
-            if paged:
-                cache.advance(Tq, host_counts, exact=counts is None or host_counts is not None)
+            cache.book_step(Tq, new_tokens)
         return attn
 
     @staticmethod

@@ -31,6 +31,10 @@ PagedKVCache (always ragged) drops the slab: rows live in pages of page_size row
 [num_pages, nkv, page_size, ...] per buffer by a PageAllocator and found through a per-sequence page table on the device
 (ops.*(..., page_table=)).  A sequence holds the pages its own rows need, a recycled slot returns its pages, and fork() lets
 two sequences share the full pages of a common prefix.
+
+PagedKVPool is the paged cache of a whole model: one allocator, one page table and one set of lengths for all layers, the
+pools carrying a leading layer dimension; pool.layer(l) is the PagedKVCache view layer l's block steps on, and swap_out /
+swap_in move a sequence's pages of every layer to pinned host memory and back (ops.kv_pages_*, csrc/oq_kvpool.hip).
 """
 import heapq
 import operator
@@ -159,6 +163,14 @@ class PackedKVCache:
         n = self.length
         return tuple(unpack_codes(c[:, :, :n], m[:, :, :n], self.code_bits).to(self.dtype)
                      for c, m in ((self.k_codes, self.k_meta), (self.v_codes, self.v_meta)))
+
+    def book_step(self, Tq, new_tokens):
+        """Book a step of Tq rows on a ragged cache, after the step's attention (which reads the pre-step lengths; the stream
+        orders the launches): new_tokens = (counts or None for all Tq, growth of the bound, the counts on the host or None) as
+        block_common._new_tokens_in returns it.  The block forwards call this."""
+        counts, grow, _ = new_tokens
+        self.lengths.add_(Tq if counts is None else counts)
+        self.length = self.length + (Tq if grow is None else grow)
 
     def reserve(self, n):
         """Room for n more rows: the capacity grows geometrically (at least doubling) and the valid rows move to the new
@@ -337,23 +349,24 @@ class PagedKVCache:
     ragged = True
     paged = True
 
-    def __init__(self, bs, nkv, hd, dtype, device, num_pages, page_size=16, max_pages=None, code_bits=None):
+    def __init__(self, bs, nkv, hd, dtype, device, num_pages, page_size=16, max_pages=None, code_bits=None, _lead=()):
+        who = type(self).__name__
         device = torch.device(device)
         if device.type != "cuda":
-            raise OQError(f"PagedKVCache needs a GPU device (got {device}); there is no CPU fallback")
+            raise OQError(f"{who} needs a GPU device (got {device}); there is no CPU fallback")
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if dtype not in _DTYPES:
-            raise OQError(f"PagedKVCache: dtype {dtype} (the packed blocks compute in bfloat16 or float32)")
+            raise OQError(f"{who}: dtype {dtype} (the packed blocks compute in bfloat16 or float32)")
         max_pages = num_pages if max_pages is None else max_pages
         if min(int(bs), int(nkv), int(hd), int(num_pages), int(max_pages)) <= 0:
-            raise OQError(f"PagedKVCache: bs {bs}, nkv {nkv}, hd {hd}, num_pages {num_pages}, max_pages {max_pages}")
+            raise OQError(f"{who}: bs {bs}, nkv {nkv}, hd {hd}, num_pages {num_pages}, max_pages {max_pages}")
         if page_size not in (16, 32, 64, 128):
-            raise OQError(f"PagedKVCache: page_size {page_size} (16, 32, 64 or 128)")
+            raise OQError(f"{who}: page_size {page_size} (16, 32, 64 or 128)")
         if int(hd) not in (64, 128):
-            raise OQError(f"PagedKVCache: head_dim {hd} (the decode kernels cover 64 and 128)")
+            raise OQError(f"{who}: head_dim {hd} (the decode kernels cover 64 and 128)")
         if code_bits is not None and code_bits not in (4, 8):
-            raise OQError(f"PagedKVCache: code_bits {code_bits} (None: float rows, 4 or 8)")
+            raise OQError(f"{who}: code_bits {code_bits} (None: float rows, 4 or 8)")
         self.bs, self.nkv, self.hd, self.dtype, self.device = int(bs), int(nkv), int(hd), dtype, device
         self.num_pages, self.page_size, self.max_pages, self.code_bits = int(num_pages), int(page_size), int(max_pages), code_bits
         self.length = 0
@@ -363,7 +376,7 @@ class PagedKVCache:
         self._bound = [0] * self.bs                         # host upper bound of each length
         self._exact = [True] * self.bs                      # ... which is the length itself (it came as a Python int)
         self.page_table = torch.full((self.bs, self.max_pages), -1, dtype=torch.int32, device=device)
-        shape = (self.num_pages, self.nkv, self.page_size)
+        shape = tuple(_lead) + (self.num_pages, self.nkv, self.page_size)      # (_lead: PagedKVPool's layer dimension)
         for name in self._buffers():
             if code_bits is None:
                 t = torch.empty(shape + (self.hd,), dtype=dtype, device=device)
@@ -425,11 +438,18 @@ class PagedKVCache:
             p.extend(self.allocator.alloc(w))
         self._upload()
 
+    def book_step(self, Tq, new_tokens):
+        """PackedKVCache.book_step, and advance() books the step in the host bounds.  The block forwards call this."""
+        counts, grow, host_counts = new_tokens
+        self.lengths.add_(Tq if counts is None else counts)
+        self.length = self.length + (Tq if grow is None else grow)
+        self.advance(Tq, host_counts, exact=counts is None or host_counts is not None)
+
     def advance(self, rows, counts=None, exact=True):
         """Book a step of `rows` rows per sequence that the kernels have appended: the host bounds grow by `counts` (the valid
         rows of each sequence as Python ints) or by `rows` -- exact=False: only an upper bound of what the sequences grew by,
         their counts being a device tensor.  With counts, the pages that only the pad rows of a right-padded step made
-        reserve() take are returned to the pool.  The block forwards call this; `lengths` and `length` are theirs to update."""
+        reserve() take are returned to the pool.  book_step() calls this after it has updated `lengths` and `length`."""
         if counts is None:
             self._bound = [bd + int(rows) for bd in self._bound]
             if not exact:
@@ -582,3 +602,339 @@ class PagedKVCache:
         return (f"PagedKVCache(bs={self.bs}, nkv={self.nkv}, hd={self.hd}, dtype={self.dtype}, length={self.length}, paged: "
                 f"page_size={self.page_size}, {self.allocator.n_free} of {self.num_pages} pages free, max_pages={self.max_pages}"
                 + ("" if self.code_bits is None else f", code_bits={self.code_bits}") + ")")
+
+
+class SwappedSequence:
+    """One sequence of a PagedKVPool in host memory (PagedKVPool.swap_out): `length` rows in `n_pages` pages, the pool's
+    geometry (layers, nkv, hd, page_size, dtype, code_bits) and, per buffer kind of the pool ("k", "v" or "k_codes", "v_codes",
+    "k_meta", "v_meta"), `buffers[kind]`: one PINNED uint8 host tensor [layers, n_pages, page_bytes] holding the raw bytes of
+    the sequence's pages in row order -- page_bytes = nkv * page_size * bytes of one row of that kind.  `event` is recorded
+    behind the last device-to-host copy on `stream`: the bytes are complete once it has passed (swap_in waits for it on another
+    stream; a host reader calls event.synchronize()).  The handle is never consumed: it can be swapped into any empty slot of
+    any pool of the same geometry, any number of times."""
+
+    def __init__(self, length, n_pages, geometry, buffers, event, stream):
+        self.length, self.n_pages, self.geometry, self.buffers, self.event, self.stream = length, n_pages, geometry, buffers, event, stream
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() for t in self.buffers.values())
+
+    def __repr__(self):
+        return f"SwappedSequence(length={self.length}, n_pages={self.n_pages}, nbytes={self.nbytes}, geometry={self.geometry})"
+
+
+class _PoolLayer(PagedKVCache):
+    """Layer l of a PagedKVPool, what layer l's block receives as past_key_value: a PagedKVCache that allocates nothing.  Its
+    pools are pool.<buffer>[l] (contiguous, so the kernels are the per-layer cache's), its page_table and lengths the pool's
+    shared tensors, and length, the pages and the allocator are read through to the pool.  reserve() and book_step(), which
+    the block forward calls, take part in the pool's step protocol; everything that changes the sequences (set_lengths, fork,
+    swap) is called on the pool."""
+
+    def __init__(self, pool, l):
+        self.pool, self.index = pool, l
+        self.bs, self.nkv, self.hd, self.dtype, self.device = pool.bs, pool.nkv, pool.hd, pool.dtype, pool.device
+        self.num_pages, self.page_size, self.max_pages, self.code_bits = pool.num_pages, pool.page_size, pool.max_pages, pool.code_bits
+        self.lengths, self.page_table = pool.lengths, pool.page_table
+        for name in pool._buffers():
+            setattr(self, name, getattr(pool, name)[l])
+
+    length = property(lambda self: self.pool.length)
+    allocator = property(lambda self: self.pool.allocator)
+    _pages = property(lambda self: self.pool._pages)
+
+    def reserve(self, n):
+        self.pool._layer_reserve(self.index, int(n))
+
+    def book_step(self, Tq, new_tokens):
+        self.pool._layer_book(self.index, int(Tq), new_tokens)
+
+    def _on_the_pool(self, what):
+        raise OQError(f"{what}: layer {self.index} is a view of {self.pool!r}; call it on the pool, for all layers at once")
+
+    def advance(self, rows, counts=None, exact=True):
+        self._on_the_pool("advance")
+
+    def set_lengths(self, lengths, bound=None):
+        self._on_the_pool("set_lengths")
+
+    def fork(self, src, dst):
+        self._on_the_pool("fork")
+
+    def clone(self):
+        self._on_the_pool("clone")
+
+    def __repr__(self):
+        return f"layer {self.index} of {self.pool!r}"
+
+
+class PagedKVPool(PagedKVCache):
+    """The paged KV cache of a whole model: `layers` layers share ONE PageAllocator, one host mirror, one page_table int32
+    [bs, max_pages], one `lengths` int32 [bs] on the device and one host bound `length`.  Storage per buffer kind is one tensor
+    with a leading layer dimension -- k / v [layers, num_pages, nkv, page_size, hd], with code_bits 4 / 8 k_codes / v_codes /
+    k_meta / v_meta in PagedKVCache's shapes behind `layers` -- and a page id names the same slot in every layer.  The
+    arguments are PagedKVCache's, checked and refused as it does.  The host side IS PagedKVCache's (reserve, advance,
+    set_lengths, fork, pages, n_free, nbytes and the sharing invariant), applied to every layer at once: a shared page has
+    reference count 2 once, and the page copies of set_lengths and fork are one ops.kv_pages_copy launch per buffer kind for all
+    layers.
+
+    layer(l) is the view layer l's block receives as past_key_value.  Step protocol: in a model step every layer's block forward
+    runs exactly once, in any order, with the same step rows Tq and the same new_tokens.  The first view whose reserve(Tq) is
+    called does the pool's reserve -- one host loop over the batch, at most one table upload -- and the others only check their
+    Tq.  After its attention a view books its step; when the last of the `layers` views has, the pool applies the step once
+    (lengths, length, the host bounds, the pad-row trim of PagedKVCache.advance).  Until then every view reads the pre-step
+    length and lengths; all launches are on one stream, which orders them.  A view that steps twice before the others, a Tq
+    or new_tokens that differs from the step's first layer, and set_lengths / fork / swap_* in mid-step raise OQError and leave
+    the pool unchanged; abort_step() discards the bookings of an unfinished step.  new_tokens given as a device tensor must be
+    the same tensor object for every layer (its values are never read).
+
+    swap_out(b) moves a sequence to pinned host memory and frees its pages, swap_in(b, handle) brings one back into fresh
+    private pages: a gather / scatter launch per buffer kind (ops.kv_pages_gather / kv_pages_scatter) through a device staging
+    buffer of swap_staging_bytes, allocated at the first swap and kept, and non-blocking copies between it and the host; the
+    kernels touch device memory only.  No call of the step path, and neither swap, reads the device (a swap may block in the
+    host allocator, see swap_out).  reserve() and advance() are the step protocol's own (the views call them through the
+    pool) and are refused in mid-step when called directly."""
+
+    def __init__(self, layers, bs, nkv, hd, dtype, device, num_pages, page_size=16, max_pages=None, code_bits=None,
+                 swap_staging_bytes=64 << 20):
+        layers = operator.index(layers)
+        if layers <= 0:
+            raise OQError(f"PagedKVPool: layers {layers}")
+        super().__init__(bs, nkv, hd, dtype, device, num_pages, page_size, max_pages, code_bits, _lead=(layers,))
+        self.layers = layers
+        biggest = max(self._page_bytes(n) for n in self._buffers())
+        if int(swap_staging_bytes) < biggest:
+            raise OQError(f"PagedKVPool: swap_staging_bytes {swap_staging_bytes} below one page of one layer ({biggest} bytes)")
+        self.swap_staging_bytes = int(swap_staging_bytes)
+        self._staging = None
+        self._step = None                   # an unfinished model step: Tq, the layers that reserved / booked, its new_tokens
+        self._copies = []                   # (src, dst) page copies queued by set_lengths / fork for one launch
+        self._views = [_PoolLayer(self, l) for l in range(layers)]
+
+    def layer(self, l):
+        """The view of layer l (created once): what layer l's block receives as past_key_value."""
+        l = operator.index(l)
+        if not 0 <= l < self.layers:
+            raise IndexError(f"layer {l} of {self.layers}")
+        return self._views[l]
+
+    def _page_bytes(self, name):
+        t = getattr(self, name)
+        return t[0, 0].numel() * t.element_size()
+
+    # ---- the step protocol ---------------------------------------------------------------------------------------------------
+    def _layer_reserve(self, l, Tq):
+        st = self._step
+        if st is None:
+            self.reserve(Tq)                # all or nothing: a refusal opens no step
+            self._step = {"Tq": Tq, "reserved": {l}, "booked": set(), "tokens": None}
+            return
+        if l in st["reserved"]:
+            raise OQError(f"{self!r}: layer {l} steps twice in one model step ({len(st['booked'])} of {self.layers} layers have "
+                          "booked it; abort_step() discards an unfinished step)")
+        if Tq != st["Tq"]:
+            raise OQError(f"{self!r}: layer {l} steps {Tq} rows, the step's first layer {st['Tq']}")
+        st["reserved"].add(l)
+
+    @staticmethod
+    def _same_tokens(a, b):
+        (ca, ga, ha), (cb, gb, hb) = a, b
+        if ha is not None or hb is not None:
+            return ha == hb and ga == gb
+        return ca is cb and ga == gb
+
+    def _layer_book(self, l, Tq, new_tokens):
+        st = self._step
+        if st is None or l not in st["reserved"] or l in st["booked"] or Tq != st["Tq"]:
+            raise OQError(f"{self!r}: layer {l} books a step of {Tq} rows it has not reserved")
+        if st["tokens"] is not None and not self._same_tokens(st["tokens"], new_tokens):
+            raise OQError(f"{self!r}: layer {l}'s new_tokens differ from the step's first layer's")
+        if st["tokens"] is None:
+            st["tokens"] = tuple(new_tokens)
+        st["booked"].add(l)
+        if len(st["booked"]) == self.layers:
+            self._step = None
+            PagedKVCache.book_step(self, Tq, st["tokens"])
+
+    def abort_step(self):
+        """Discard the bookings of an unfinished model step: lengths, length and the host bounds stay the pre-step ones (pages
+        its reserve took stay with their sequences, as after PagedKVCache.reserve)."""
+        self._step = None
+
+    def _idle(self, what):
+        if self._step is not None:
+            st = self._step
+            raise OQError(f"{self!r}: {what} in mid-step ({len(st['booked'])} of {self.layers} layers have booked a step of "
+                          f"{st['Tq']} rows; abort_step() discards it)")
+
+    def book_step(self, Tq, new_tokens):
+        raise OQError(f"{self!r}: the layers' views step (pool.layer(l) as past_key_value), not the pool")
+
+    def reserve(self, n):
+        """PagedKVCache.reserve for every layer at once.  The first view of a model step calls it; called directly it is refused
+        in mid-step, like every other call that moves the host state behind the step protocol."""
+        self._idle("reserve")
+        super().reserve(n)
+
+    def advance(self, rows, counts=None, exact=True):
+        """PagedKVCache.advance on the pool's host bounds.  The pool calls it when the last layer has booked a step; called
+        directly it is refused in mid-step."""
+        self._idle("advance")
+        super().advance(rows, counts, exact)
+
+    # ---- model-wide set_lengths / fork: PagedKVCache's, the page copies batched into one launch per buffer kind ----------------
+    def _copy_page(self, src, dst):
+        # a queued copy must not write a page that an earlier queued copy still reads (a source both sharers have left is free
+        # again and may be handed out as a destination): launch what is queued first
+        if any(dst == s for s, _ in self._copies):
+            self._flush_copies()
+        self._copies.append((src, dst))
+
+    def _flush_copies(self):
+        from . import ops
+        pairs, self._copies = self._copies, []
+        if not pairs:
+            return
+        ids = torch.tensor(pairs, dtype=torch.int32).t().contiguous().to(self.device, non_blocking=True)
+        for name in self._buffers():
+            ops.kv_pages_copy(getattr(self, name), ids[0], ids[1])
+
+    def set_lengths(self, lengths, bound=None):
+        """PagedKVCache.set_lengths for every layer at once."""
+        self._idle("set_lengths")
+        try:
+            super().set_lengths(lengths, bound)
+            self._flush_copies()
+        finally:
+            self._copies = []               # (after an exception: never launch stale pairs on pages that changed owner)
+
+    def fork(self, src, dst):
+        """PagedKVCache.fork for every layer at once: the shared pages gain one reference, not one per layer."""
+        self._idle("fork")
+        try:
+            super().fork(src, dst)
+            self._flush_copies()
+        finally:
+            self._copies = []
+
+    # ---- swap to host --------------------------------------------------------------------------------------------------------
+    @property
+    def geometry(self):
+        return (self.layers, self.nkv, self.hd, self.page_size, self.dtype, self.code_bits)
+
+    def _chunks(self, name, n):
+        """The (layer range, page range) pieces of a transfer of n pages of every layer that fit the staging buffer: whole
+        layers while a layer's pages fit, else page ranges of one layer."""
+        pb = self._page_bytes(name)
+        if n * pb <= self.swap_staging_bytes:
+            step = self.swap_staging_bytes // (n * pb)
+            return [(l, min(l + step, self.layers), 0, n) for l in range(0, self.layers, step)]
+        step = self.swap_staging_bytes // pb
+        return [(l, l + 1, p, min(p + step, n)) for l in range(self.layers) for p in range(0, n, step)]
+
+    def _stage(self):
+        if self._staging is None:
+            self._staging = torch.empty(self.swap_staging_bytes, dtype=torch.uint8, device=self.device)
+        return self._staging
+
+    def _slot(self, what, b):
+        b = operator.index(b)
+        if not 0 <= b < self.bs:
+            raise OQError(f"{what}: sequence {b} of a batch of {self.bs}")
+        return b
+
+    def swap_out(self, b):
+        """Move sequence b to host memory: all ceil(length / page_size) pages of every layer, shared ones included, are gathered
+        into the staging buffer and copied to a SwappedSequence's pinned tensors (in chunks when they exceed the staging buffer;
+        stream order makes its reuse safe); then b's references are released, lengths[b] and its host bound become 0 and the
+        table is uploaded.  The host must know b's length exactly (as fork needs it).  Nothing here reads the device, and the
+        handle's event tells when the bytes have arrived.  The call can still block on the host: the page ids go up from
+        pageable memory (the runtime stages such a copy, as for the table upload), and the first handle of a size allocates
+        pinned host memory, which later ones of that size find in torch's pinned-memory cache."""
+        from . import ops
+        self._idle("swap_out")
+        b = self._slot("swap_out", b)
+        if not self._exact[b]:
+            raise OQError(f"swap_out: the host holds only an upper bound of sequence {b}'s length (set_lengths with Python ints)")
+        length = self._bound[b]
+        n = self._need(length)
+        ids = torch.tensor(self._pages[b][:n], dtype=torch.int32).to(self.device, non_blocking=True)
+        buffers = {}
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            for name in self._buffers():
+                pool, pb = getattr(self, name), self._page_bytes(name)
+                host = torch.empty((self.layers, n, pb), dtype=torch.uint8, pin_memory=True)
+                for l0, l1, p0, p1 in (self._chunks(name, n) if n else ()):
+                    stage = self._stage()[:(l1 - l0) * (p1 - p0) * pb]
+                    ops.kv_pages_gather(pool[l0:l1], ids[p0:p1], stage)
+                    host[l0:l1, p0:p1].copy_(stage.view(l1 - l0, p1 - p0, pb), non_blocking=True)
+                buffers[name] = host
+            event = torch.cuda.Event()
+            event.record(stream)
+        self.allocator.release(self._pages[b])
+        self._pages[b] = []
+        self._bound[b] = 0
+        self.lengths[b:b + 1].zero_()
+        self._upload()
+        return SwappedSequence(length, n, self.geometry, buffers, event, stream)
+
+    def swap_in(self, b, handle):
+        """Bring a swapped-out sequence into slot b, which must be empty with its length known to the host: n_pages fresh
+        private pages (all or nothing), the handle's bytes copied host -> staging and scattered into the pages of every layer,
+        lengths[b] and the host bound set to the handle's length (`length` grows to it if it is below), the table uploaded.
+        Sharing is not restored: the sequence owns all its pages.  The handle stays valid.  A geometry that differs, a slot
+        that is not empty and a pool without the pages raise OQError before anything changes."""
+        from . import ops
+        self._idle("swap_in")
+        b = self._slot("swap_in", b)
+        if not isinstance(handle, SwappedSequence):
+            raise OQError(f"swap_in: expected a SwappedSequence, got {type(handle).__name__}")
+        if handle.geometry != self.geometry:
+            raise OQError(f"swap_in: {handle!r} does not fit the geometry {self.geometry} of {self!r}")
+        if self._bound[b] != 0 or not self._exact[b]:
+            raise OQError(f"swap_in: sequence {b} is not empty (set_lengths with 0 for it first)")
+        n = handle.n_pages
+        if n > self.max_pages:
+            raise OQError(f"{self!r}: swap_in of {handle.length} rows takes sequence {b} beyond max_pages = {self.max_pages}")
+        own = [pg for pg in self._pages[b] if self.allocator.refcount(pg) == 1]
+        if n > self.allocator.n_free + len(own):
+            raise OQError(f"{self!r}: swap_in needs {n} pages, {self.allocator.n_free + len(own)} are free")
+        self.allocator.release(self._pages[b])
+        self._pages[b] = self.allocator.alloc(n)
+        ids = torch.tensor(self._pages[b], dtype=torch.int32).to(self.device, non_blocking=True)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            if stream != handle.stream:
+                stream.wait_event(handle.event)
+            for name in self._buffers():
+                pool, pb, host = getattr(self, name), self._page_bytes(name), handle.buffers[name]
+                for l0, l1, p0, p1 in (self._chunks(name, n) if n else ()):
+                    stage = self._stage()[:(l1 - l0) * (p1 - p0) * pb]
+                    stage.view(l1 - l0, p1 - p0, pb).copy_(host[l0:l1, p0:p1], non_blocking=True)
+                    ops.kv_pages_scatter(stage, pool[l0:l1], ids[p0:p1])
+        self.lengths[b:b + 1].copy_(torch.tensor([handle.length], dtype=torch.int32), non_blocking=True)
+        self._bound[b] = handle.length
+        self.length = max(self.length, handle.length)
+        self._upload()
+
+    # ---- the rest of the surface ---------------------------------------------------------------------------------------------
+    def sequence(self, b):
+        raise OQError(f"{self!r}: sequence(b) is a layer's (pool.layer(l).sequence(b))")
+
+    def clone(self):
+        self._idle("clone")
+        c = PagedKVPool(self.layers, self.bs, self.nkv, self.hd, self.dtype, self.device, self.num_pages, self.page_size,
+                        self.max_pages, code_bits=self.code_bits, swap_staging_bytes=self.swap_staging_bytes)
+        for name in self._buffers():
+            getattr(c, name).copy_(getattr(self, name))
+        c.allocator = self.allocator.clone()
+        c._pages, c._bound, c._exact, c.length = [list(p) for p in self._pages], list(self._bound), list(self._exact), self.length
+        c.page_table.copy_(self.page_table)
+        c.lengths.copy_(self.lengths)
+        return c
+
+    def __repr__(self):
+        return (f"PagedKVPool(layers={self.layers}, bs={self.bs}, nkv={self.nkv}, hd={self.hd}, dtype={self.dtype}, "
+                f"length={self.length}, paged: page_size={self.page_size}, {self.allocator.n_free} of {self.num_pages} pages free, "
+                f"max_pages={self.max_pages}" + ("" if self.code_bits is None else f", code_bits={self.code_bits}") + ")")

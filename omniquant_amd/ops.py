@@ -2081,6 +2081,74 @@ def extend_attention_codes(q, cache, L, scale, lengths, page_table=None, out=Non
     return o
 
 
+def _kv_pages_args(fn, pool, ids, flat=None, flat_name=None):
+    """Validate a page move of a model-wide pool (kvcache.PagedKVPool), on the host and before any device call: `ids` =
+    ((name, tensor), ...) are int32 1-D tensors of one length on the pool's device, `pool` a contiguous [layers, num_pages, ...]
+    tensor whose pages (everything behind the first two dimensions) are a multiple of 16 bytes, `flat` (gather's dst, scatter's
+    src; None: no such buffer) a contiguous tensor of layers * n * page_bytes bytes on that device.  The values are never read.
+    Returns (contiguous ids, layers, num_pages, page_bytes, n)."""
+    if not torch.is_tensor(pool) or pool.dim() < 3:
+        what = f"{tuple(pool.shape)} {pool.dtype}" if torch.is_tensor(pool) else type(pool).__name__
+        raise C.OQError(f"{fn}: pool must be a [layers, num_pages, ...] tensor, got {what}")
+    out = []
+    for name, t in ids:
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1:
+            what = f"{tuple(t.shape)} {t.dtype}" if torch.is_tensor(t) else type(t).__name__
+            raise C.OQError(f"{fn}: {name} must be an int32 1-D device tensor, got {what}")
+        if t.device != pool.device:
+            raise C.OQError(f"{fn}: {name} on {t.device}, the pool on {pool.device}")
+        if t.shape[0] != ids[0][1].shape[0]:
+            raise C.OQError(f"{fn}: {name} names {t.shape[0]} pages, {ids[0][0]} {ids[0][1].shape[0]}")
+        out.append(t.contiguous())
+    n = out[0].shape[0]
+    layers, num_pages = pool.shape[0], pool.shape[1]
+    page_bytes = pool[0, 0].numel() * pool.element_size() if layers and num_pages else 0
+    if page_bytes <= 0 or page_bytes % 16:
+        raise C.OQError(f"{fn}: pool {tuple(pool.shape)} {pool.dtype} has pages of {page_bytes} bytes (page_bytes must be a "
+                        "positive multiple of 16)")
+    if not pool.is_contiguous():
+        raise C.OQError(f"{fn}: pool {tuple(pool.shape)} with strides {pool.stride()} is not contiguous")
+    if flat_name is not None:
+        want = layers * n * page_bytes
+        if not torch.is_tensor(flat) or not flat.is_contiguous() or flat.numel() * flat.element_size() != want:
+            what = f"{tuple(flat.shape)} {flat.dtype}" + ("" if flat.is_contiguous() else " (not contiguous)") \
+                if torch.is_tensor(flat) else type(flat).__name__
+            raise C.OQError(f"{fn}: {flat_name} {what} (expected {want} contiguous bytes: [{layers}, {n}, {page_bytes}])")
+        if flat.device != pool.device:
+            raise C.OQError(f"{fn}: {flat_name} on {flat.device}, the pool on {pool.device}")
+    return out, layers, num_pages, page_bytes, n
+
+
+def kv_pages_gather(pool, page_ids, dst=None):
+    """dst [layers, n, page_bytes] <- pages page_ids of every layer of pool [layers, num_pages, ...] in ONE launch
+    (oq_kv_pages_gather, csrc/oq_kvpool.hip).  pool: contiguous (a slice pool[l0:l1] of layers is), any dtype; a page is
+    everything behind its first two dimensions, page_bytes a multiple of 16.  page_ids: int32 [n] on the pool's device, never
+    read by the host; an id outside [0, num_pages) is skipped and dst keeps its bytes there; ids may repeat.  dst: a contiguous
+    tensor of layers * n * page_bytes bytes on that device (None: a fresh uint8 [layers, n, page_bytes]).  Returns dst."""
+    (ids,), layers, num_pages, pb, n = _kv_pages_args("kv_pages_gather", pool, (("page_ids", page_ids),), dst,
+                                                      None if dst is None else "dst")
+    if dst is None:
+        dst = torch.empty((layers, n, pb), dtype=torch.uint8, device=pool.device)
+    C.call("oq_kv_pages_gather", C.ptr(pool), num_pages, pb, num_pages * pb, layers, C.ptr(ids), n, C.ptr(dst), C.stream())
+    return dst
+
+
+def kv_pages_scatter(src, pool, page_ids):
+    """Pages page_ids of every layer of pool <- src [layers, n, page_bytes]: the reverse of kv_pages_gather in one launch
+    (oq_kv_pages_scatter).  An id outside [0, num_pages) is skipped and the pool untouched; the valid ids must be distinct."""
+    (ids,), layers, num_pages, pb, n = _kv_pages_args("kv_pages_scatter", pool, (("page_ids", page_ids),), src, "src")
+    C.call("oq_kv_pages_scatter", C.ptr(src), C.ptr(pool), num_pages, pb, num_pages * pb, layers, C.ptr(ids), n, C.stream())
+    return pool
+
+
+def kv_pages_copy(pool, src_ids, dst_ids):
+    """pool[:, dst_ids[i]] <- pool[:, src_ids[i]] for every layer in one launch (oq_kv_pages_copy).  A pair with src == dst, or
+    with either id outside [0, num_pages), is skipped.  The valid dst ids must be distinct and none of them another pair's src."""
+    (s, d), layers, num_pages, pb, n = _kv_pages_args("kv_pages_copy", pool, (("src_ids", src_ids), ("dst_ids", dst_ids)))
+    C.call("oq_kv_pages_copy", C.ptr(pool), num_pages, pb, num_pages * pb, layers, C.ptr(s), C.ptr(d), n, C.stream())
+    return pool
+
+
 def mask_is_causal(attention_mask):
     """True iff the additive attention mask ([T,T] or [bs,1,T,T]) is exactly the causal one: 0 on/below the diagonal
     and <= -3e4 above it -- finfo(float32).min, or finfo(float16).min = -65504 as transformers builds it for the fp16
