@@ -545,6 +545,36 @@ int oq_kv_pages_scatter(const void* src, void* pool, int64_t num_pages, int64_t 
 int oq_kv_pages_copy(void* pool, int64_t num_pages, int64_t page_bytes, int64_t layer_stride_bytes, int64_t layers,
                      const int32_t* src_ids, const int32_t* dst_ids, int64_t n, void* stream);
 
+/*   Tree attention for speculative decoding (csrc/oq_extend.hip, the TREE form of the chunked-prefill kernel; scores, mask,
+ *      softmax and PV of models/int_llama_layer.py:143-163 over the past_key_value of :121-135, the mask being a token tree's
+ *      instead of the causal one).  The step's Tq <= 64 rows are the nodes of a tree of draft tokens appended at lens[b] + t; with
+ *      len = clamp(lens[b], 0, L_bound - Tq), cache row j is visible to node t iff j < len, or u = j - len < Tq and bit u of node
+ *      t's ancestor set is set.  anc: int32 [anc_bs][Tq][2] on the device, anc_bs 1 (one tree for the batch) or bs; (low, high)
+ *      words of the 64-bit set whose bit u is set iff u is t or an ancestor of t -- bits above t are ignored, so a row never
+ *      sees more than the causal kernel's row t would, and rows at or beyond lens[b] + Tq are never read.  One entry point for
+ *      all storage forms: code_bits 0 (k / v bf16 rows, k_meta / v_meta ignored), 4 or 8 (code rows and their metas);
+ *      table == NULL: slabs [bs, nkv, cap, ...], else page pools and (max_pages, num_pages, page_size) as in the _paged forms
+ *      (cap is then ignored).  Split plan, workspace (oq_attn_extend_workspace) and combine are oq_attn_extend's; with a chain
+ *      (parent(t) = t - 1) the output is that kernel's bit for bit.  Tq > 64, a dtype other than bf16 and head dims other than
+ *      64 / 128 return OQ_E_UNSUPPORTED; a null anc, anc_bs outside {1, bs} and code_bits outside {0, 4, 8} OQ_E_ARG; nothing
+ *      is launched then. */
+int oq_attn_tree(const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o, int dtype,
+                 int code_bits, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* table,
+                 int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound, const int32_t* anc,
+                 int64_t anc_bs, float scale, void* workspace, int64_t workspace_bytes, void* stream);
+/*   Committing the accepted path of a verified tree (csrc/oq_kvpool.hip; no counterpart in the reference, whose past_key_value
+ *      of models/int_llama_layer.py:121-135 only grows by whole steps).  buf is one buffer kind of a cache as raw bytes: slab
+ *      [layers][bs][nkv][cap][row_bytes], or with table != NULL page pools [layers][num_pages][nkv][page_size][row_bytes]; layers
+ *      are layer_stride_bytes apart (layers == 1: ignored).  accept: int32 [bs][Tq] on the device, the accepted node ids in path
+ *      order, padded with -1.  For every (layer, sequence, kv head) entry i is valid while i <= accept[b][i] < Tq and it lies
+ *      strictly above the previous entry; row lens[b] + accept[b][i] moves to row lens[b] + i, and the first invalid entry ends
+ *      the sequence's moves.  A source or destination row outside [0, cap), or in a page outside [0, num_pages), skips that move.
+ *      One launch for all layers: each thread owns one column of up to 16 bytes and does its moves in ascending i, which is what
+ *      makes the in-place compaction safe.  row_bytes a multiple of 4, 1 <= Tq <= 64. */
+int oq_kv_tree_commit(void* buf, int64_t row_bytes, int64_t layers, int64_t layer_stride_bytes, int64_t bs, int nkv, int64_t cap,
+                      const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens,
+                      const int32_t* accept, int64_t Tq, void* stream);
+
 /* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,

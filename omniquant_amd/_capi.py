@@ -129,6 +129,10 @@ SIGNATURES = {
     "oq_kv_pages_gather": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
     "oq_kv_pages_scatter": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
     "oq_kv_pages_copy": [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    # tree attention of a speculative step and the commit of its accepted path: one entry point each for all storage forms
+    "oq_attn_tree": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _i64,
+                     _vp, _i64, _f32, _vp, _i64, _vp],
+    "oq_kv_tree_commit": [_vp, _i64, _i64, _i64, _i64, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,

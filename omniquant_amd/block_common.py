@@ -150,8 +150,32 @@ class QuantBlockMixin:
             return None
         return self._positions(position_ids, cache.length, bsz, T, device)
 
+    @staticmethod
+    def _tree_in(tree, cache, attention_mask, position_ids, new_tokens, bsz, T, rope=True):
+        """The checks of a speculative TREE step (forward(..., tree=kvcache.TokenTree)), made before the cache changes, and its
+        RoPE positions: int64 [bs, T] = lengths[b] + depth(t), one elementwise op on the device with no host read (None
+        without rope: OPT).  The step needs a ragged bfloat16 cache with a past, takes no attention_mask, position_ids or
+        new_tokens, and its T rows are the tree's nodes."""
+        from ._capi import OQError
+        from .kvcache import TokenTree
+        if not isinstance(tree, TokenTree):
+            raise OQError(f"tree: expected a kvcache.TokenTree, got {type(tree).__name__}")
+        if attention_mask is not None or position_ids is not None or new_tokens is not None:
+            raise OQError("a tree step takes no attention_mask, position_ids or new_tokens: the tree is the mask, a node rotates at "
+                          "lengths[b] + its depth, and all Tq nodes are appended")
+        if cache is None or not getattr(cache, "ragged", False):
+            raise OQError("a tree step needs a ragged cache as past_key_value (PackedKVCache(ragged=True), a PagedKVCache or a "
+                          "pool's layer view)")
+        if cache.dtype != torch.bfloat16 or cache.length <= 0:
+            raise OQError(f"a tree step needs a bfloat16 cache with a past (length > 0), got {cache!r}")
+        if tree.Tq != T or tree.bs not in (None, bsz):
+            raise OQError(f"{tree!r} does not fit a step of {bsz} x {T} rows (one row per node)")
+        if not rope:
+            return None
+        return cache.lengths[:, None].to(torch.int64) + tree.to(cache.device).depth
+
     def _cached_attention(self, q, k, v, cache, attention_mask, scale, cos=None, sin=None, positions=None, head_bits=None,
-                          new_tokens=(None, None, None)):
+                          new_tokens=(None, None, None), tree=None):
         """Attention of this step's q [bs, Tq, nh, hd] over the cache plus this step's k / v, which are appended to it (rotated
         by cos / sin at `positions` when given: LLaMA).  Without a past (prefill) the attention is exactly the no-cache path's
         (_packed_attention on the rotated q / k); with a past it is oq_attn_decode, with no host synchronisation.
@@ -178,7 +202,11 @@ class QuantBlockMixin:
         page_table=cache.page_table; reserve() gives every sequence the pages the step's rows need (uploading the table only
         if one was added).  Nothing else about the step changes.
         After the attention a ragged cache books the step itself (cache.book_step): lengths, the bound `length` and, paged, the
-        host bounds; a layer view of a PagedKVPool books it with its pool, which applies it once all layers have."""
+        host bounds; a layer view of a PagedKVPool books it with its pool, which applies it once all layers have.
+        tree (a kvcache.TokenTree, checked by _tree_in, which also builds `positions` = lengths[b] + depth): the step's Tq rows
+        are the nodes of a tree of draft tokens.  They are reserved and appended like any step's rows, attended by
+        ops.tree_attention (always, also below EXTEND_MIN_TQ) and booked as a TREE step (cache.book_tree_step): no length
+        moves until cache.commit_tree."""
         from . import ops
         from ._capi import OQError
         bsz, Tq = q.shape[0], q.shape[1]
@@ -224,6 +252,8 @@ class QuantBlockMixin:
             if mask is not None and mask.shape[0] != bsz:
                 mask = mask.expand(bsz, 1, Tq, L)
             attn = self._packed_attention(qr, k if kr is None else kr, v if vr is None else vr, mask, scale)
+        elif tree is not None:
+            attn = ops.tree_attention(qr, cache, L, scale, lens, tree, **paged)
         elif self._extend_step(cache, qr, Tq):
             if cache.code_bits is not None:
                 attn = ops.extend_attention_codes(qr, cache, L, scale, lens, **paged)
@@ -235,7 +265,10 @@ class QuantBlockMixin:
             attn = ops.decode_attention(qr, cache.k, cache.v, L, scale, attention_mask, lengths=lens, **paged)
         if lens is not None:
             # (after the attention, which reads the pre-step lengths; the stream orders the launches)
-            cache.book_step(Tq, new_tokens)
+            if tree is not None:
+                cache.book_tree_step(Tq)
+            else:
+                cache.book_step(Tq, new_tokens)
         return attn
 
     @staticmethod

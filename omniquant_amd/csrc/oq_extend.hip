@@ -21,6 +21,7 @@
 #include "oq_common.h"
 #include "oq_attn_dev.h"
 #include "oq_kv_dev.h"
+#include <type_traits>
 
 namespace {
 
@@ -56,6 +57,14 @@ struct ExtP {
     int64_t Tq, cap, L, chunk;
     int nh, nkv, ns, nqt;
     float zs;                           // scale * log2(e)
+};
+
+// The TREE form (oq_attn_tree): the step's Tq <= 64 rows are the nodes of a token tree instead of a causal chunk.  anc holds
+// one 64-bit set per node as (low, high) words, bit u set iff node u is the node itself or one of its ancestors (so only bits
+// <= t are set for node t); cache row j is visible to node t iff j < len, or bit j - len of the node's set is set.
+struct TreeP : ExtP {
+    const uint2* anc;                   // [1 | bs][Tq]
+    int64_t anc_bstride;                // Tq, or 0 when one tree serves the batch
 };
 
 // LDS image of a [64 rows][HD] bf16 tile: 16-byte chunks, XOR-swizzled per row (HD 128: oq_attn.hip's swz; HD 64: rows of 8
@@ -156,11 +165,14 @@ struct Staged {
 // One key tile for one wave.  DIAG: some (query, key) pair of the tile is masked for this wave: key 16kb + 4g + i of the tile
 // is masked for the lane's query of block qb iff 16kb + i > dq[qb] (dq = last visible row - first row of the tile - 4g), and,
 // PAGED, when the row was not loaded.  A query row with no visible key yet keeps m = -inf, l = 0, o = 0.
+// TREE: dq[qb] is instead the 64-bit visibility set of the lane's query over the tile's keys, shifted down by 4g: key
+// 16kb + 4g + i is masked iff bit 16kb + i is clear.
 // meta: the tile's [K scale | V scale | loaded flag] x 64.  MID: called between the S^T MFMAs and the softmax.
-template <int HD, int NQB, bool DIAG, int CODES, bool PAGED, typename MID>
+template <int HD, int NQB, bool DIAG, int CODES, bool PAGED, bool TREE, typename DQ, typename MID>
 __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const float* meta, const bf16x8 (&qf)[NQB][HD / 32],
-                                         f32x4 (&o)[NQB][HD / 16], float (&m)[NQB], float (&l)[NQB], const int (&dq)[NQB],
+                                         f32x4 (&o)[NQB][HD / 16], float (&m)[NQB], float (&l)[NQB], const DQ (&dq)[NQB],
                                          float zs, int lane, MID&& mid) {
+    static_assert(std::is_same<DQ, typename std::conditional<TREE, uint64_t, int>::type>::value, "dq: int, or the TREE bit sets");
     constexpr int KS = HD / 32, DB = HD / 16;
     const int g = lane >> 4;
     f32x4 st[4][NQB];
@@ -197,7 +209,10 @@ __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const f
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float z = st[kb][qb][i] * f[i];
-                if (DIAG && (16 * kb + i > dq[qb] || (PAGED && ok[i] == 0.f))) z = -INFINITY;
+                bool hid;
+                if constexpr (TREE) hid = ((dq[qb] >> (16 * kb + i)) & 1u) == 0;
+                else hid = 16 * kb + i > dq[qb];
+                if (DIAG && (hid || (PAGED && ok[i] == 0.f))) z = -INFINITY;
                 st[kb][qb][i] = z;
             }
     }
@@ -256,8 +271,8 @@ __device__ __forceinline__ void ext_tile(const char* Ks, const char* Vs, const f
     }
 }
 
-template <int HD, int NQB, int CODES, bool PAGED>
-__global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
+template <int HD, int NQB, int CODES, bool PAGED, bool TREE = false>
+__global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(typename std::conditional<TREE, TreeP, ExtP>::type p) {
     constexpr int TILE = 64 * HD * 2, KS = HD / 32, DB = HD / 16, QT = 64 * NQB;
     using St = Staged<HD, CODES>;
     constexpr int NP = St::NP;
@@ -284,6 +299,16 @@ __global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
         const bf16_t* qp = p.q + ((b * Tq + tq[qb]) * p.nh + (int64_t)kvh * rep + (r % rep)) * HD;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qf[qb][ks] = *reinterpret_cast<const bf16x8*>(qp + 32 * ks + 8 * g);
+    }
+    // TREE: the query node's ancestor set, read once next to its q fragments; bits above the node itself are dropped, so the
+    // causal bounds below (jend, vis_hi) stay upper bounds of what a row sees whatever the buffer holds
+    uint64_t am[NQB];
+    if constexpr (TREE) {
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) {
+            const uint2 wd = p.anc[b * p.anc_bstride + tq[qb]];
+            am[qb] = (((uint64_t)wd.y << 32) | wd.x) & (~uint64_t(0) >> (63 - (int)tq[qb]));     // Tq <= 64
+        }
     }
     const bool live = qw0 < R;                                       // wave-uniform: the wave holds a real query row
     const int64_t vis_lo = len + (qw0 < R ? qw0 : R - 1) / rep;      // last row its first / last query row sees
@@ -360,13 +385,31 @@ __global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
             }
         };
         if (live && j0 <= vis_hi) {      // wave-uniform: this wave has at least one unmasked (query, key) pair in the tile
-            int dq[NQB];
+            if constexpr (TREE) {
+                // the tile's keys are tree rows j0 - len + 0 .. 63: the set shifted to the tile, rows of the past (below len)
+                // all visible.  A tile needs the per-element mask as soon as it reaches row len, not only on the diagonal; the
+                // TREE form runs the masked body on every tile, as the PAGED forms do (a tile of the past has all bits set).
+                // A second, unmasked body inlined next to it costs the slab forms 40 to 50 VGPRs and makes head_dim 128 spill.
+                const int64_t s = j0 - len;
+                uint64_t tv[NQB];
 #pragma unroll
-            for (int qb = 0; qb < NQB; ++qb) dq[qb] = (int)(len + tq[qb] - j0) - 4 * g;
-            if (PAGED || j0 + 63 > vis_lo)
-                ext_tile<HD, NQB, true, CODES, PAGED>(Ks, Vs, meta + cur * 192, qf, o, m, l, dq, p.zs, lane, mid);
-            else
-                ext_tile<HD, NQB, false, CODES, PAGED>(Ks, Vs, meta + cur * 192, qf, o, m, l, dq, p.zs, lane, mid);
+                for (int qb = 0; qb < NQB; ++qb) {
+                    uint64_t vv = ~uint64_t(0);
+                    if (s >= 64) vv = 0;
+                    else if (s >= 0) vv = am[qb] >> s;
+                    else if (s > -64) vv = (am[qb] << -s) | (~uint64_t(0) >> (64 + s));
+                    tv[qb] = vv >> (4 * g);
+                }
+                ext_tile<HD, NQB, true, CODES, PAGED, true>(Ks, Vs, meta + cur * 192, qf, o, m, l, tv, p.zs, lane, mid);
+            } else {
+                int dq[NQB];
+#pragma unroll
+                for (int qb = 0; qb < NQB; ++qb) dq[qb] = (int)(len + tq[qb] - j0) - 4 * g;
+                if (PAGED || j0 + 63 > vis_lo)
+                    ext_tile<HD, NQB, true, CODES, PAGED, false>(Ks, Vs, meta + cur * 192, qf, o, m, l, dq, p.zs, lane, mid);
+                else
+                    ext_tile<HD, NQB, false, CODES, PAGED, false>(Ks, Vs, meta + cur * 192, qf, o, m, l, dq, p.zs, lane, mid);
+            }
         } else {
             mid();
         }
@@ -406,33 +449,45 @@ __global__ void __launch_bounds__(EXT_THREADS, 2) attn_extend_kernel(ExtP p) {
     }
 }
 
-template <int HD, int NQB, int CODES, bool PAGED>
-void launch_extend(const ExtP& p, int64_t bs, hipStream_t st) {
-    hipLaunchKernelGGL((attn_extend_kernel<HD, NQB, CODES, PAGED>), dim3((unsigned)(p.nqt * p.ns), p.nkv, bs), dim3(EXT_THREADS), 0, st, p);
+template <int HD, int NQB, int CODES, bool PAGED, bool TREE, typename P>
+void launch_extend(const P& p, int64_t bs, hipStream_t st) {
+    hipLaunchKernelGGL((attn_extend_kernel<HD, NQB, CODES, PAGED, TREE>), dim3((unsigned)(p.nqt * p.ns), p.nkv, bs), dim3(EXT_THREADS), 0, st, p);
     if (p.ns > 1)
         hipLaunchKernelGGL((attn_decode_combine_kernel<bf16_t, HD>), dim3(bs * (int64_t)p.nh * p.Tq), dim3(HD), 0, st,
                            (const float*)p.ws, p.o, p.Tq, p.nh, p.nkv, p.ns);
 }
 
-template <int HD, int NQB>
-void launch_extend_kv(int codes, const ExtP& p, int64_t bs, hipStream_t st) {
+template <int HD, int NQB, bool TREE, typename P>
+void launch_extend_kv(int codes, const P& p, int64_t bs, hipStream_t st) {
     if (codes == 8) {
-        if (p.pm.table) launch_extend<HD, NQB, 8, true>(p, bs, st);
-        else launch_extend<HD, NQB, 8, false>(p, bs, st);
+        if (p.pm.table) launch_extend<HD, NQB, 8, true, TREE>(p, bs, st);
+        else launch_extend<HD, NQB, 8, false, TREE>(p, bs, st);
     } else if (codes) {
-        if (p.pm.table) launch_extend<HD, NQB, 4, true>(p, bs, st);
-        else launch_extend<HD, NQB, 4, false>(p, bs, st);
+        if (p.pm.table) launch_extend<HD, NQB, 4, true, TREE>(p, bs, st);
+        else launch_extend<HD, NQB, 4, false, TREE>(p, bs, st);
     } else {
-        if (p.pm.table) launch_extend<HD, NQB, 0, true>(p, bs, st);
-        else launch_extend<HD, NQB, 0, false>(p, bs, st);
+        if (p.pm.table) launch_extend<HD, NQB, 0, true, TREE>(p, bs, st);
+        else launch_extend<HD, NQB, 0, false, TREE>(p, bs, st);
+    }
+}
+
+template <bool TREE, typename P>
+void launch_extend_hd(int hd, int nqb, int codes, const P& p, int64_t bs, hipStream_t st) {
+    if (hd == 64) {
+        if (nqb == 1) launch_extend_kv<64, 1, TREE>(codes, p, bs, st);
+        else launch_extend_kv<64, 2, TREE>(codes, p, bs, st);
+    } else {
+        if (nqb == 1) launch_extend_kv<128, 1, TREE>(codes, p, bs, st);
+        else launch_extend_kv<128, 2, TREE>(codes, p, bs, st);
     }
 }
 
 // codes (0, 4 or 8): k / v are the code buffers of a cache of that width and k_meta / v_meta its (scale, zero-point) pairs; 0: a
-// bf16 cache's buffers.  pm.table: the buffers are page pools and cap = max_pages * page size.
+// bf16 cache's buffers.  pm.table: the buffers are page pools and cap = max_pages * page size.  anc (oq_attn_tree): the TREE form
+// with the nodes' ancestor sets, anc_bs (1 or bs) of them.
 int extend(const char* fn, int codes, const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o,
            int dtype, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, int64_t L, const int32_t* lens, const PageMap& pm,
-           float scale, void* workspace, int64_t workspace_bytes, void* stream) {
+           float scale, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* anc = nullptr, int64_t anc_bs = 0) {
     if (!oq_attn_extend_supported(dtype, Tq, hd)) {
         oq_set_error("%s: dtype %d, head_dim %d (bf16 with head_dim 64 or 128; oq_attn_decode_* serves the rest)", fn, dtype, hd);
         return OQ_E_UNSUPPORTED;
@@ -459,12 +514,14 @@ int extend(const char* fn, int codes, const void* q, const void* k, const void* 
     const ExtP p{(const bf16_t*)q, (bf16_t*)o, (float*)workspace, k, v, (const f32x2*)k_meta, (const f32x2*)v_meta, lens, pm, Tq, cap, L,
                  chunk, nh, nkv, ns, (int)nqt, scale * 1.4426950408889634f};
     hipStream_t st = (hipStream_t)stream;
-    if (hd == 64) {
-        if (nqb == 1) launch_extend_kv<64, 1>(codes, p, bs, st);
-        else launch_extend_kv<64, 2>(codes, p, bs, st);
+    if (anc) {
+        TreeP tp;
+        static_cast<ExtP&>(tp) = p;
+        tp.anc = reinterpret_cast<const uint2*>(anc);
+        tp.anc_bstride = anc_bs > 1 ? Tq : 0;
+        launch_extend_hd<true>(hd, nqb, codes, tp, bs, st);
     } else {
-        if (nqb == 1) launch_extend_kv<128, 1>(codes, p, bs, st);
-        else launch_extend_kv<128, 2>(codes, p, bs, st);
+        launch_extend_hd<false>(hd, nqb, codes, p, bs, st);
     }
     OQ_CHECK_LAUNCH(fn);
     return OQ_OK;
@@ -531,4 +588,26 @@ extern "C" int oq_attn_extend_codes8_paged(const void* q, const void* k_codes, c
     OQ_PAGE_MAP("oq_attn_extend_codes8_paged");
     return extend("oq_attn_extend_codes8_paged", 8, q, k_codes, v_codes, k_meta, v_meta, o, dtype, bs, Tq, nh, nkv, hd, cap, L_bound,
                   lens, pm, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int oq_attn_tree(const void* q, const void* k, const void* v, const float* k_meta, const float* v_meta, void* o, int dtype,
+                            int code_bits, int64_t bs, int64_t Tq, int nh, int nkv, int hd, int64_t cap, const int32_t* table,
+                            int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens, int64_t L_bound,
+                            const int32_t* anc, int64_t anc_bs, float scale, void* workspace, int64_t workspace_bytes,
+                            void* stream) {
+    const char* fn = "oq_attn_tree";
+    if (Tq > 64) {
+        oq_set_error("%s: Tq %lld (a token tree has at most 64 nodes: one 64-bit ancestor set per node)", fn, (long long)Tq);
+        return OQ_E_UNSUPPORTED;
+    }
+    OQ_CHECK_ARG(code_bits == 0 || code_bits == 4 || code_bits == 8, "%s: code_bits %d (0: bf16 rows, 4 or 8)", fn, code_bits);
+    OQ_CHECK_ARG(anc && (uintptr_t)anc % 8 == 0, "%s: anc (int32 [1 | bs, Tq, 2] on the device, 8-byte aligned)", fn);
+    OQ_CHECK_ARG(anc_bs == 1 || anc_bs == bs, "%s: anc_bs %lld (1 or bs = %lld)", fn, (long long)anc_bs, (long long)bs);
+    OQ_CHECK_ARG(lens, "%s: null lens", fn);
+    PageMap pm = NO_PAGES;
+    if (table) {
+        if (const int rc = page_map(fn, table, max_pages, num_pages, page_size, &pm, &cap)) return rc;
+    }
+    return extend(fn, code_bits, q, k, v, code_bits ? k_meta : nullptr, code_bits ? v_meta : nullptr, o, dtype, bs, Tq, nh, nkv, hd, cap,
+                  L_bound, lens, pm, scale, workspace, workspace_bytes, stream, anc, anc_bs);
 }

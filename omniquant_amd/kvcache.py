@@ -35,6 +35,12 @@ two sequences share the full pages of a common prefix.
 PagedKVPool is the paged cache of a whole model: one allocator, one page table and one set of lengths for all layers, the
 pools carrying a leading layer dimension; pool.layer(l) is the PagedKVCache view layer l's block steps on, and swap_out /
 swap_in move a sequence's pages of every layer to pinned host memory and back (ops.kv_pages_*, csrc/oq_kvpool.hip).
+
+TokenTree is the host description of a tree of draft tokens (speculative decoding).  A block forward with tree= appends the
+tree's Tq nodes at rows lengths[b] + t of a ragged cache and attends them under the tree's mask (ops.tree_attention) without
+moving any length: the cache only remembers that a tree step is pending.  commit_tree(tree, accept) then compacts the accepted
+root path's rows to lengths[b] + 0, 1, ... in every buffer (ops.kv_tree_commit) and grows the lengths by the accepted counts.
+Any other change of state (a normal step, set_lengths, fork, swap_*, abort_step) drops a pending tree: its rows are scratch.
 """
 import heapq
 import operator
@@ -60,7 +66,136 @@ def unpack_codes(codes, meta, bits=4):
     return (c - meta[..., 1:2]) * meta[..., 0:1]
 
 
+class _TreeOnDevice:
+    """TokenTree.to(device): anc int32 [1 | bs, Tq, 2] (low word = nodes 0..31, high word = 32..63 of each node's ancestor
+    set) and depth int64 [1 | bs, Tq]."""
+
+    def __init__(self, anc, depth):
+        self.anc, self.depth = anc, depth
+
+
+class TokenTree:
+    """A tree of Tq draft tokens for one speculative step, or one such tree per sequence.  parents: a sequence of Tq ints, or bs
+    sequences of Tq ints each; parents[t] in [-1, t) names node t's parent (so the order is topological), -1 hangs the node off
+    the committed past, and several roots are allowed.  1 <= Tq <= 64.  Pure Python: no device is needed to build one.
+
+    Tq, bs (None: one tree for the whole batch), height = largest depth + 1; depth (roots 0) and ancestors (one 64-bit int per
+    node, bit u set iff u is the node or one of its ancestors: only bits <= t) are lists over the nodes, or with per-sequence
+    trees lists of such lists; path(t, b=0) gives the node ids from a root down to t, ascending.  to(device) uploads the masks
+    and depths once per device and caches them."""
+
+    MAX_NODES = 64
+
+    def __init__(self, parents):
+        try:
+            outer = list(parents)
+            per_seq = len(outer) > 0 and not hasattr(outer[0], "__index__")
+            trees = [[operator.index(p) for p in t] for t in outer] if per_seq else [[operator.index(p) for p in outer]]
+        except TypeError:
+            raise OQError(f"TokenTree: parents must be Tq ints or bs sequences of Tq ints, got {parents!r}") from None
+        Tq = len(trees[0])
+        if not 1 <= Tq <= self.MAX_NODES:
+            raise OQError(f"TokenTree: {Tq} nodes (1 to {self.MAX_NODES})")
+        if any(len(t) != Tq for t in trees):
+            raise OQError(f"TokenTree: per-sequence trees of {[len(t) for t in trees]} nodes (one Tq for the batch; pad with leaves)")
+        for t in trees:
+            for node, par in enumerate(t):
+                if not -1 <= par < node:
+                    raise OQError(f"TokenTree: parents[{node}] = {par} outside [-1, {node}) (a parent precedes its children; -1: "
+                                  "a root)")
+        self.Tq, self.bs = Tq, len(trees) if per_seq else None
+        self.parents = trees if per_seq else trees[0]
+        depth, anc = [], []
+        for t in trees:
+            d, a = [], []
+            for node, par in enumerate(t):
+                d.append(0 if par < 0 else d[par] + 1)
+                a.append((1 << node) | (0 if par < 0 else a[par]))
+            depth.append(d)
+            anc.append(a)
+        self.height = max(max(d) for d in depth) + 1
+        self.depth, self.ancestors = (depth, anc) if per_seq else (depth[0], anc[0])
+        self._trees, self._depth, self._anc = trees, depth, anc
+        self._on = {}
+
+    def _tree(self, b):
+        return 0 if self.bs is None else operator.index(b)
+
+    def path(self, t, b=0):
+        """The node ids from a root to node t (of sequence b's tree), ascending."""
+        t = operator.index(t)
+        if not 0 <= t < self.Tq:
+            raise IndexError(f"node {t} of a tree of {self.Tq}")
+        anc = self._anc[self._tree(b)][t]
+        return [u for u in range(t + 1) if anc >> u & 1]
+
+    def is_root_path(self, nodes, b=0):
+        """Whether `nodes` is empty or a path from a root downwards (of sequence b's tree): each node the child of the one before."""
+        par = self._trees[self._tree(b)]
+        prev = -1
+        for n in nodes:
+            if not 0 <= n < self.Tq or par[n] != prev:
+                return False
+            prev = n
+        return True
+
+    def to(self, device):
+        """The tree on `device` (uploaded once, then cached): an object with anc int32 [1 | bs, Tq, 2] and depth int64
+        [1 | bs, Tq]."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        on = self._on.get(device)
+        if on is None:
+            words = [[[a & 0xFFFFFFFF, a >> 32] for a in tree] for tree in self._anc]
+            anc = torch.tensor(words, dtype=torch.int64).to(torch.int32)         # (wraps bit 31 into the sign)
+            on = _TreeOnDevice(anc.to(device), torch.tensor(self._depth, dtype=torch.int64).to(device))
+            self._on[device] = on
+        return on
+
+    def __repr__(self):
+        return f"TokenTree(Tq={self.Tq}, height={self.height}" + ("" if self.bs is None else f", bs={self.bs}") + ")"
+
+
+def _accept_in(who, cache, tree, accept):
+    """commit_tree's arguments, checked before anything changes: (accept int32 [bs, Tq] on the device, counts int32 [bs] on the
+    device, the counts as Python ints or None for the device form)."""
+    if not isinstance(tree, TokenTree):
+        raise OQError(f"{who}: expected a TokenTree, got {type(tree).__name__}")
+    Tq, bs = tree.Tq, cache.bs
+    if cache._tree_pending is None:
+        raise OQError(f"{who}: {cache!r} has no pending tree step (a forward with tree= books one; any other change of state "
+                      "drops it)")
+    if cache._tree_pending != Tq:
+        raise OQError(f"{who}: {tree!r}, the pending tree step has {cache._tree_pending} nodes")
+    if tree.bs not in (None, bs):
+        raise OQError(f"{who}: {tree!r} for a batch of {bs}")
+    if torch.is_tensor(accept):
+        if accept.dtype != torch.int32 or tuple(accept.shape) != (bs, Tq) or accept.device != cache.device:
+            raise OQError(f"{who}: accept must be an int32 [{bs}, {Tq}] tensor on {cache.device} (node ids in path order, padded "
+                          f"with -1), got {tuple(accept.shape)} {accept.dtype} on {accept.device}")
+        accept = accept.contiguous()
+        counts = (accept >= 0).to(torch.int32).cummin(dim=1).values.sum(dim=1, dtype=torch.int32)
+        return accept, counts, None
+    try:
+        paths = [[operator.index(n) for n in path] for path in accept]
+    except TypeError:
+        raise OQError(f"{who}: accept must be {bs} lists of node ids or an int32 [{bs}, {Tq}] device tensor") from None
+    if len(paths) != bs:
+        raise OQError(f"{who}: {len(paths)} paths for a batch of {bs}")
+    for b, path in enumerate(paths):
+        if not tree.is_root_path(path, b):
+            raise OQError(f"{who}: sequence {b}'s path {path} is not a root path of {tree!r} (empty, or a root followed by a "
+                          "child of each previous node)")
+    rows = [path + [-1] * (Tq - len(path)) for path in paths]
+    host = [len(path) for path in paths]
+    return (torch.tensor(rows, dtype=torch.int32).to(cache.device, non_blocking=True),
+            torch.tensor(host, dtype=torch.int32).to(cache.device, non_blocking=True), host)
+
+
 class PackedKVCache:
+    _tree_pending = None                # the node count of a tree step whose rows wait for commit_tree (ragged caches)
+
     def __init__(self, bs, nkv, hd, dtype, device, capacity=0, code_bits=None, ragged=False):
         device = torch.device(device)
         if device.type != "cuda":
@@ -137,6 +272,7 @@ class PackedKVCache:
             lengths = torch.tensor(seq, dtype=torch.int32)
         if not 0 <= top <= self.capacity:
             raise OQError(f"set_lengths: bound {top} outside the capacity {self.capacity}")
+        self._tree_pending = None
         self.lengths.copy_(lengths)
         self.length = top
 
@@ -169,13 +305,36 @@ class PackedKVCache:
         orders the launches): new_tokens = (counts or None for all Tq, growth of the bound, the counts on the host or None) as
         block_common._new_tokens_in returns it.  The block forwards call this."""
         counts, grow, _ = new_tokens
+        self._tree_pending = None
         self.lengths.add_(Tq if counts is None else counts)
         self.length = self.length + (Tq if grow is None else grow)
+
+    def book_tree_step(self, Tq):
+        """Book a TREE step of Tq nodes (a block forward with tree=): lengths and length do not move; the cache remembers that
+        Tq tree rows at lengths[b] + t wait for commit_tree.  The block forwards call this."""
+        self._tree_pending = int(Tq)
+
+    def commit_tree(self, tree, accept):
+        """Make the accepted root path of the pending tree step each sequence's next rows.  accept: bs lists of node ids, each
+        empty or a root path of `tree` (checked; `length` grows by the longest), or an int32 [bs, Tq] device tensor of node ids
+        in path order padded with -1 (not validated, the caller guarantees root paths; the counts are computed on the device,
+        nothing is read back, and `length` grows by tree.height).  One ops.kv_tree_commit launch per buffer, then lengths +=
+        counts.  Without a pending tree step, or with a tree of another Tq, OQError and nothing changes."""
+        from . import ops
+        if not self.ragged:
+            raise OQError("commit_tree: not a ragged cache (PackedKVCache(..., ragged=True))")
+        acc, counts, host = _accept_in("commit_tree", self, tree, accept)
+        for name in self._buffers():
+            ops.kv_tree_commit(getattr(self, name), self.lengths, acc)
+        self._tree_pending = None
+        self.lengths.add_(counts)
+        self.length = min(self.length + (tree.height if host is None else max(host)), self.capacity)
 
     def reserve(self, n):
         """Room for n more rows: the capacity grows geometrically (at least doubling) and the valid rows move to the new
         buffers.  A cache sized to prompt + max_new_tokens up front never reallocates."""
         need = self.length + int(n)
+        self._tree_pending = None       # (a new step begins: the rows of an uncommitted tree are scratch)
         if need <= self.capacity:
             return
         self._allocate(max(need, 2 * self.capacity, 16), keep=self)
@@ -348,6 +507,7 @@ class PagedKVCache:
 
     ragged = True
     paged = True
+    _tree_pending = None                # as PackedKVCache's
 
     def __init__(self, bs, nkv, hd, dtype, device, num_pages, page_size=16, max_pages=None, code_bits=None, _lead=()):
         who = type(self).__name__
@@ -432,6 +592,7 @@ class PagedKVCache:
                               f"({self.capacity} rows)")
         if sum(want) > self.allocator.n_free:
             raise OQError(f"{self!r}: {n} more rows per sequence need {sum(want)} pages, {self.allocator.n_free} are free")
+        self._tree_pending = None       # (a new step begins: the rows of an uncommitted tree are scratch; a refusal keeps them)
         if not any(want):
             return
         for w, p in zip(want, self._pages):
@@ -441,9 +602,36 @@ class PagedKVCache:
     def book_step(self, Tq, new_tokens):
         """PackedKVCache.book_step, and advance() books the step in the host bounds.  The block forwards call this."""
         counts, grow, host_counts = new_tokens
+        self._tree_pending = None
         self.lengths.add_(Tq if counts is None else counts)
         self.length = self.length + (Tq if grow is None else grow)
         self.advance(Tq, host_counts, exact=counts is None or host_counts is not None)
+
+    def book_tree_step(self, Tq):
+        """PackedKVCache.book_tree_step: nothing moves, no page is trimmed; the pages reserve() took for the tree's rows stay
+        with their sequences until commit_tree (or a later step's trim)."""
+        self._tree_pending = int(Tq)
+
+    def _commit_buffers(self, acc):
+        from . import ops
+        for name in self._buffers():        # (a pool's buffers carry the layer dimension: one launch serves all layers)
+            ops.kv_tree_commit(getattr(self, name), self.lengths, acc, page_table=self.page_table)
+
+    def commit_tree(self, tree, accept):
+        """PackedKVCache.commit_tree on paged storage.  Host form: the host bounds grow by the exact counts and the pages
+        beyond them return to the pool (a table upload only if one did).  Device form: the bounds grow by tree.height and
+        become upper bounds, as with a device new_tokens.  The commit writes only rows at or beyond a sequence's length, which
+        lie in pages it owns alone (the sharing invariant)."""
+        acc, counts, host = _accept_in("commit_tree", self, tree, accept)
+        self._commit_buffers(acc)
+        self._tree_pending = None
+        self.lengths.add_(counts)
+        if host is None:
+            self.length = min(self.length + tree.height, self.capacity)
+            PagedKVCache.advance(self, tree.height, None, exact=False)
+        else:
+            self.length = self.length + max(host)
+            PagedKVCache.advance(self, 0, host)
 
     def advance(self, rows, counts=None, exact=True):
         """Book a step of `rows` rows per sequence that the kernels have appended: the host bounds grow by `counts` (the valid
@@ -507,6 +695,7 @@ class PagedKVCache:
         freed = sum(1 for pg in set(dropped) if dropped.count(pg) == refs(pg))
         if len(copies) + sum(fresh) > self.allocator.n_free + freed:
             raise OQError(f"{self!r}: set_lengths needs {len(copies) + sum(fresh)} pages, {self.allocator.n_free + freed} are free")
+        self._tree_pending = None
         self.allocator.release(dropped)
         for b, p in enumerate(self._pages):
             del p[keep[b]:]
@@ -539,6 +728,7 @@ class PagedKVCache:
         own = [pg for pg in self._pages[dst] if self.allocator.refcount(pg) == 1]
         if part > self.allocator.n_free + len(own):
             raise OQError(f"{self!r}: fork needs a page for the partial last page, none is free")
+        self._tree_pending = None
         self.allocator.release(self._pages[dst])
         shared = self._pages[src][:full]
         self.allocator.retain(shared)
@@ -649,6 +839,14 @@ class _PoolLayer(PagedKVCache):
     def book_step(self, Tq, new_tokens):
         self.pool._layer_book(self.index, int(Tq), new_tokens)
 
+    def book_tree_step(self, Tq):
+        self.pool._layer_book(self.index, int(Tq), (None, None, None), tree=True)
+
+    def commit_tree(self, tree, accept):
+        self._on_the_pool("commit_tree")
+
+    _tree_pending = property(lambda self: self.pool._tree_pending)
+
     def _on_the_pool(self, what):
         raise OQError(f"{what}: layer {self.index} is a view of {self.pool!r}; call it on the pool, for all layers at once")
 
@@ -684,7 +882,7 @@ class PagedKVPool(PagedKVCache):
     Tq.  After its attention a view books its step; when the last of the `layers` views has, the pool applies the step once
     (lengths, length, the host bounds, the pad-row trim of PagedKVCache.advance).  Until then every view reads the pre-step
     length and lengths; all launches are on one stream, which orders them.  A view that steps twice before the others, a Tq
-    or new_tokens that differs from the step's first layer, and set_lengths / fork / swap_* in mid-step raise OQError and leave
+    or new_tokens that differs from the step's first layer, a tree step (tree=) in one layer and a normal one in another, and set_lengths / fork / swap_* in mid-step raise OQError and leave
     the pool unchanged; abort_step() discards the bookings of an unfinished step.  new_tokens given as a device tensor must be
     the same tensor object for every layer (its values are never read).
 
@@ -727,7 +925,7 @@ class PagedKVPool(PagedKVCache):
         st = self._step
         if st is None:
             self.reserve(Tq)                # all or nothing: a refusal opens no step
-            self._step = {"Tq": Tq, "reserved": {l}, "booked": set(), "tokens": None}
+            self._step = {"Tq": Tq, "reserved": {l}, "booked": set(), "tokens": None, "tree": None}
             return
         if l in st["reserved"]:
             raise OQError(f"{self!r}: layer {l} steps twice in one model step ({len(st['booked'])} of {self.layers} layers have "
@@ -743,10 +941,14 @@ class PagedKVPool(PagedKVCache):
             return ha == hb and ga == gb
         return ca is cb and ga == gb
 
-    def _layer_book(self, l, Tq, new_tokens):
+    def _layer_book(self, l, Tq, new_tokens, tree=False):
         st = self._step
         if st is None or l not in st["reserved"] or l in st["booked"] or Tq != st["Tq"]:
             raise OQError(f"{self!r}: layer {l} books a step of {Tq} rows it has not reserved")
+        if st["tree"] is not None and st["tree"] != tree:
+            raise OQError(f"{self!r}: layer {l} books a {'tree' if tree else 'normal'} step, the step's first layer a "
+                          f"{'tree' if st['tree'] else 'normal'} one")
+        st["tree"] = tree
         if st["tokens"] is not None and not self._same_tokens(st["tokens"], new_tokens):
             raise OQError(f"{self!r}: layer {l}'s new_tokens differ from the step's first layer's")
         if st["tokens"] is None:
@@ -754,12 +956,22 @@ class PagedKVPool(PagedKVCache):
         st["booked"].add(l)
         if len(st["booked"]) == self.layers:
             self._step = None
-            PagedKVCache.book_step(self, Tq, st["tokens"])
+            if st["tree"]:
+                self._tree_pending = Tq     # a tree step: nothing advances, commit_tree does
+            else:
+                PagedKVCache.book_step(self, Tq, st["tokens"])
 
     def abort_step(self):
         """Discard the bookings of an unfinished model step: lengths, length and the host bounds stay the pre-step ones (pages
-        its reserve took stay with their sequences, as after PagedKVCache.reserve)."""
+        its reserve took stay with their sequences, as after PagedKVCache.reserve).  A pending tree step is dropped too."""
         self._step = None
+        self._tree_pending = None
+
+    def commit_tree(self, tree, accept):
+        """PagedKVCache.commit_tree for every layer at once, after the tree step of all layers: one ops.kv_tree_commit launch
+        per buffer kind.  Refused in mid-step."""
+        self._idle("commit_tree")
+        super().commit_tree(tree, accept)
 
     def _idle(self, what):
         if self._step is not None:
@@ -872,6 +1084,7 @@ class PagedKVPool(PagedKVCache):
                 buffers[name] = host
             event = torch.cuda.Event()
             event.record(stream)
+        self._tree_pending = None
         self.allocator.release(self._pages[b])
         self._pages[b] = []
         self._bound[b] = 0
@@ -900,6 +1113,7 @@ class PagedKVPool(PagedKVCache):
         own = [pg for pg in self._pages[b] if self.allocator.refcount(pg) == 1]
         if n > self.allocator.n_free + len(own):
             raise OQError(f"{self!r}: swap_in needs {n} pages, {self.allocator.n_free + len(own)} are free")
+        self._tree_pending = None
         self.allocator.release(self._pages[b])
         self._pages[b] = self.allocator.alloc(n)
         ids = torch.tensor(self._pages[b], dtype=torch.int32).to(self.device, non_blocking=True)

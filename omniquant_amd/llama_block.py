@@ -303,15 +303,20 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
                     ln1=self.input_layernorm, ln2=self.post_attention_layernorm)
 
     def forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None,
-                output_attentions=False, use_cache=False, new_tokens=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                output_attentions=False, use_cache=False, new_tokens=None, tree=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """new_tokens (packed blocks with a ragged PackedKVCache as past_key_value only): the valid rows of this right-padded
-        step per sequence, a Python sequence of ints or an int32 [bs] device tensor with 0 <= n_b <= T; None: all T."""
+        step per sequence, a Python sequence of ints or an int32 [bs] device tensor with 0 <= n_b <= T; None: all T.
+        tree (packed blocks with a ragged bfloat16 cache that has a past only): a kvcache.TokenTree whose nodes the T rows of
+        this speculative step are; the cache's commit_tree then keeps a root path (block_common._cached_attention)."""
         if self.__dict__.get("_oq_packed") is not None:
             return self._packed_forward(hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache,
-                                        new_tokens)
+                                        new_tokens, tree)
         if new_tokens is not None:
             from ._capi import OQError
             raise OQError("new_tokens needs a packed block and a ragged PackedKVCache as past_key_value")
+        if tree is not None:
+            from ._capi import OQError
+            raise OQError("tree needs a packed block and a ragged cache as past_key_value")
         hidden_states, back = self._enter(hidden_states)
         residual = hidden_states
         a = self.self_attn
@@ -344,7 +349,7 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
 
     @torch.no_grad()
     def _packed_forward(self, hidden_states, attention_mask, position_ids, past_key_value, output_attentions, use_cache,
-                        new_tokens=None):
+                        new_tokens=None, tree=None):
         """Real-quant inference (realquant.pack_block): norm -> q / k / v PackedLinears -> RoPE -> attention -> o_proj (+ residual
         in its store) -> norm -> gate / up -> SiLU * up -> down_proj (+ residual).  With a KV cache (past_key_value or use_cache;
         models/int_llama_layer.py:121-135,177,264-265) q / k are rotated at their positions and k / v appended to the cache in one
@@ -353,7 +358,7 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         A kvcache.PagedKVCache (paged, ragged storage; the caller creates it) is taken in the same way."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if self.__dict__["_oq_packed"].get("act_quant"):
-            return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens)
+            return self._packed_forward_a4(hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens, tree)
         x, back = self._enter(hidden_states)
         a, m = self.self_attn, self.mlp
         bsz, T, _ = x.shape
@@ -362,14 +367,19 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         cache = None
         if past_key_value is not None or use_cache:
             cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x)
+        if tree is not None:
+            pos = self._tree_in(tree, cache, attention_mask, position_ids, new_tokens, bsz, T)
+        elif cache is not None:
             pos = self._step_positions(position_ids, cache, bsz, T, x.device)
+        if cache is not None:
             cos, sin = a._rope_table(cache.length + T, x.device)
         h = self.input_layernorm(x)
         q = a.q_proj(h).view(bsz, T, nh, hd)
         k = a.k_proj(h).view(bsz, T, nkv, hd)
         v = a.v_proj(h).view(bsz, T, nkv, hd)
         if cache is not None:
-            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos, new_tokens=counts)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0 / math.sqrt(hd), cos, sin, pos, new_tokens=counts,
+                                          tree=tree)
         else:
             cos, sin = a._rope_tables(position_ids, T, x.device)
             q, k = ops.RopeFn.apply(q, cos, sin), ops.RopeFn.apply(k, cos, sin)
@@ -393,7 +403,7 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         return ops.act_codes(norm(x2), 4)
 
     @torch.no_grad()
-    def _packed_forward_a4(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens=None):
+    def _packed_forward_a4(self, hidden_states, attention_mask, position_ids, past_key_value, use_cache, new_tokens=None, tree=None):
         """W4A4 real-quant inference: norm -> 4-bit per-token codes (one set for q, k, v) -> integer q / k / v linears (fp32
         outputs: nothing is rounded to 16 bits in front of the head quantisers) -> RoPE + head quantisers (+ KV-cache append)
         in one launch -> attention on the quantised q / k / v -> codes -> integer o_proj (+ residual in its epilogue) -> norm
@@ -412,6 +422,8 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
             raise OQError(f"the W4A4 packed path covers head_dim 64 and 128 (oq_kv_append_quant), not {hd}")
         cd = x.dtype
         counts = self._new_tokens_in(new_tokens, past_key_value, bsz, T, x.device)
+        if tree is not None and past_key_value is None:
+            self._tree_in(tree, None, attention_mask, position_ids, new_tokens, bsz, T)      # (refused: no cache)
         x2 = ops.cast(hidden_states, torch.float32).reshape(bsz * T, H)      # (exact widening of the caller's values)
         hint = self._norm_codes(self.input_layernorm, x2)
         f32 = torch.float32
@@ -422,9 +434,13 @@ class QuantLlamaDecoderLayer(QuantBlockMixin, nn.Module):
         cache = None
         if past_key_value is not None or use_cache:
             cache = self._kv_cache_in(past_key_value, bsz, T, nkv, hd, x, head_bits=4)
-            pos = self._step_positions(position_ids, cache, bsz, T, x.device)
+            if tree is not None:
+                pos = self._tree_in(tree, cache, attention_mask, position_ids, new_tokens, bsz, T)
+            else:
+                pos = self._step_positions(position_ids, cache, bsz, T, x.device)
             cos, sin = a._rope_table(cache.length + T, x.device)
-            attn = self._cached_attention(q, k, v, cache, attention_mask, scale, cos, sin, pos, head_bits=4, new_tokens=counts)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, scale, cos, sin, pos, head_bits=4, new_tokens=counts,
+                                          tree=tree)
         else:
             cos, sin = a._rope_tables(position_ids, T, x.device)
             qr, kr, vr = (torch.empty(t.shape, dtype=cd, device=x.device) for t in (q, k, v))

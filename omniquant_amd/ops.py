@@ -2081,6 +2081,121 @@ def extend_attention_codes(q, cache, L, scale, lengths, page_table=None, out=Non
     return o
 
 
+def tree_attention(q, cache, L, scale, lengths, tree, page_table=None, out=None, workspace=None):
+    """Attention of a speculative TREE step (oq_attn_tree, the TREE form of csrc/oq_extend.hip): the Tq <= 64 rows of q
+    [bs, Tq, nh, hd] (bfloat16, hd 64 or 128) are the nodes of `tree` (a kvcache.TokenTree, one tree for the batch or one per
+    sequence; or its int32 [1 | bs, Tq, 2] `anc` tensor on the device), whose k / v rows the step has appended at rows
+    lengths[b] + t.  Node t attends the committed past (rows < lengths[b]) plus itself and its ancestors, nothing else.
+    `cache`: a ragged bfloat16 cache of any kind (PackedKVCache(ragged=True), PagedKVCache, a pool's layer view; float rows, 4-
+    or 8-bit codes) or its buffers, (k, v) or (k_codes, v_codes, k_meta, v_meta); page_table: the buffers are page pools (taken
+    from a paged cache object by itself).  lengths, L, out and workspace are extend_attention's, as are the split plan and the
+    rows never read; with a chain as the tree the output is extend_attention's bit for bit.  Tree steps always run this kernel,
+    also below block_common.EXTEND_MIN_TQ."""
+    fn = "tree_attention"
+    if not torch.is_tensor(q) or q.dim() != 4:
+        raise C.OQError(f"{fn}: q must be a [bs, Tq, nh, hd] tensor")
+    if not q.is_cuda:
+        raise C.OQError(f"{fn}: q on {q.device}: the tree attention needs GPU tensors; there is no CPU fallback")
+    bs, Tq, nh, hd = q.shape
+    if isinstance(cache, (tuple, list)):
+        bufs = tuple(cache)
+    else:
+        bufs = (cache.k, cache.v) if cache.code_bits is None else (cache.k_codes, cache.v_codes, cache.k_meta, cache.v_meta)
+        if page_table is None and getattr(cache, "paged", False):
+            page_table = cache.page_table
+    if len(bufs) not in (2, 4) or not all(torch.is_tensor(t) and t.dim() == 4 for t in bufs):
+        raise C.OQError(f"{fn}: a cache, its (k, v) buffers or its (k_codes, v_codes, k_meta, v_meta) buffers expected")
+    if Tq > 64:
+        raise C.OQError(f"{fn}: Tq {Tq} (a token tree has at most 64 nodes)")
+    nkv = bufs[0].shape[1]
+    if len(bufs) == 4:
+        bits = _code_bits(bufs[0], hd)
+        row = hd if bits == 8 else hd // 2
+        kinds = ((bufs[0], row, torch.uint8), (bufs[1], row, torch.uint8), (bufs[2], 2, torch.float32), (bufs[3], 2, torch.float32))
+    else:
+        bits = 0
+        kinds = ((bufs[0], hd, q.dtype), (bufs[1], hd, q.dtype))
+    pages = None
+    if page_table is not None:
+        if hd not in (64, 128):
+            raise C.OQError(f"{fn}: head_dim {hd} (64 or 128)")
+        pages = _page_pool(fn, page_table, lengths, 0, None, bs, nkv, kinds)
+        cap = pages[1] * pages[3]
+    elif bits:
+        if bufs[0].shape[0] != bs:
+            raise C.OQError(f"{fn}: (k_codes, v_codes, k_meta, v_meta) for a batch of {bs} expected")
+        cap = _code_buffers(fn, *bufs, bs, nkv, hd, bits)
+    else:
+        k_cache, v_cache = bufs
+        if tuple(k_cache.shape) != tuple(v_cache.shape) or k_cache.shape[0] != bs or k_cache.shape[3] != hd \
+                or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
+            raise C.OQError(f"{fn}: caches {tuple(k_cache.shape)} {k_cache.dtype} do not fit q {tuple(q.shape)} {q.dtype}")
+        cap = k_cache.shape[2]
+    from .kvcache import TokenTree
+    if not torch.is_tensor(tree) and not isinstance(tree, TokenTree):
+        raise C.OQError(f"{fn}: tree must be a kvcache.TokenTree or its int32 [1 | {bs}, {Tq}, 2] anc tensor, got {type(tree).__name__}")
+    anc = tree if torch.is_tensor(tree) else tree.to(q.device).anc
+    if anc.dtype != torch.int32 or anc.dim() != 3 or anc.shape[0] not in (1, bs) or tuple(anc.shape[1:]) != (Tq, 2):
+        raise C.OQError(f"{fn}: the tree's ancestor sets {tuple(anc.shape)} {anc.dtype} (int32 [1 | {bs}, {Tq}, 2]: a tree of the "
+                        "step's Tq nodes)")
+    if anc.device != q.device:
+        raise C.OQError(f"{fn}: the tree's ancestor sets on {anc.device}, q on {q.device}")
+    anc = anc.contiguous()
+    q, lengths, o, workspace, ws_n = _extend_args(fn, q, lengths, bs, bufs[0].device, Tq, L, cap, nh, nkv, out, workspace)
+    meta = (C.fptr(bufs[2]), C.fptr(bufs[3])) if bits else (None, None)
+    table = (C.ptr(pages[0]), *pages[1:]) if pages else (None, 0, 0, 0)
+    C.call("oq_attn_tree", C.ptr(q), C.ptr(bufs[0]), C.ptr(bufs[1]), *meta, C.ptr(o), C.dt(q), bits, bs, Tq, nh, nkv, hd, cap, *table,
+           C.ptr(lengths), int(L), C.ptr(anc), anc.shape[0], float(scale), C.ptr(workspace), ws_n, C.stream())
+    return o
+
+
+def kv_tree_commit(buffer, lengths, accept, page_table=None):
+    """Make the accepted root path of a verified token tree a sequence's next rows (oq_kv_tree_commit, csrc/oq_kvpool.hip): in
+    ONE launch over all layers, row lengths[b] + accept[b, i] of `buffer` moves to row lengths[b] + i, for i = 0, 1, ... while
+    accept[b, i] is a valid entry (i <= accept[b, i] < Tq, strictly above the previous one; the first other value, the -1
+    padding for one, ends sequence b's moves).  buffer: one buffer kind of a ragged cache, any dtype, contiguous:
+    [bs, nkv, cap, x] or, for all layers at once, [layers, bs, nkv, cap, x]; with page_table (int32 [bs, max_pages]) the page
+    pools [num_pages, nkv, PS, x] or [layers, num_pages, nkv, PS, x].  lengths int32 [bs] and accept int32 [bs, Tq] live on the
+    buffer's device and are never read by the host.  Rows outside the capacity and pages the table does not hold are skipped.
+    Only rows at or beyond lengths[b] are written.  Returns buffer."""
+    fn = "kv_tree_commit"
+    if not torch.is_tensor(buffer) or buffer.dim() not in (4, 5):
+        what = f"{tuple(buffer.shape)}" if torch.is_tensor(buffer) else type(buffer).__name__
+        raise C.OQError(f"{fn}: buffer must be a [(layers,) bs | num_pages, nkv, cap | PS, x] tensor, got {what}")
+    if not buffer.is_cuda:
+        raise C.OQError(f"{fn}: buffer on {buffer.device}: the commit needs GPU tensors; there is no CPU fallback")
+    if not buffer.is_contiguous():
+        raise C.OQError(f"{fn}: buffer {tuple(buffer.shape)} with strides {buffer.stride()} is not contiguous")
+    layers = buffer.shape[0] if buffer.dim() == 5 else 1
+    lead, nkv, rows, x = buffer.shape[-4:]
+    row_bytes = x * buffer.element_size()
+    if not torch.is_tensor(accept) or accept.dtype != torch.int32 or accept.dim() != 2 or not 1 <= accept.shape[1] <= 64:
+        what = f"{tuple(accept.shape)} {accept.dtype}" if torch.is_tensor(accept) else type(accept).__name__
+        raise C.OQError(f"{fn}: accept must be an int32 [bs, Tq <= 64] tensor, got {what}")
+    bs, Tq = accept.shape
+    if accept.device != buffer.device:
+        raise C.OQError(f"{fn}: accept on {accept.device}, the buffer on {buffer.device}")
+    lengths = _ragged_lengths(fn, lengths, bs, buffer.device)
+    if page_table is not None:
+        if rows not in PAGE_SIZES:
+            raise C.OQError(f"{fn}: pool {tuple(buffer.shape)} has a page size of {rows} rows (one of {PAGE_SIZES})")
+        if not torch.is_tensor(page_table) or page_table.dtype != torch.int32 or page_table.dim() != 2 or page_table.shape[0] != bs \
+                or page_table.shape[1] <= 0 or page_table.device != buffer.device:
+            what = f"{tuple(page_table.shape)} {page_table.dtype} on {page_table.device}" if torch.is_tensor(page_table) \
+                else type(page_table).__name__
+            raise C.OQError(f"{fn}: page_table must be an int32 [{bs}, max_pages] tensor on {buffer.device}, got {what}")
+        page_table = page_table.contiguous()
+        table = (C.ptr(page_table), page_table.shape[1], lead, rows)
+        cap = 0
+    else:
+        if lead != bs:
+            raise C.OQError(f"{fn}: buffer {tuple(buffer.shape)} for a batch of {bs} (accept {tuple(accept.shape)})")
+        table, cap = (None, 0, 0, 0), rows
+    C.call("oq_kv_tree_commit", C.ptr(buffer), row_bytes, layers, lead * nkv * rows * row_bytes, bs, nkv, cap, *table, C.ptr(lengths),
+           C.ptr(accept.contiguous()), Tq, C.stream())
+    return buffer
+
+
 def _kv_pages_args(fn, pool, ids, flat=None, flat_name=None):
     """Validate a page move of a model-wide pool (kvcache.PagedKVPool), on the host and before any device call: `ids` =
     ((name, tensor), ...) are int32 1-D tensors of one length on the pool's device, `pool` a contiguous [layers, num_pages, ...]

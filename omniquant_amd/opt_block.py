@@ -96,10 +96,13 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
                 use_cache=False, past_key_value=None, **kwargs) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         if self.__dict__.get("_oq_packed") is not None:
             return self._packed_forward(hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value,
-                                        kwargs.get("new_tokens"))
+                                        kwargs.get("new_tokens"), kwargs.get("tree"))
         if kwargs.get("new_tokens") is not None:
             from ._capi import OQError
             raise OQError("new_tokens needs a packed block and a ragged PackedKVCache as past_key_value")
+        if kwargs.get("tree") is not None:
+            from ._capi import OQError
+            raise OQError("tree needs a packed block and a ragged cache as past_key_value")
         if use_cache or output_attentions:
             raise NotImplementedError("the calibration hot path runs without KV cache / attention outputs")
         hidden_states, back = self._enter(hidden_states)
@@ -139,11 +142,12 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
 
     @torch.no_grad()
     def _packed_forward(self, hidden_states, attention_mask, layer_head_mask, output_attentions, use_cache, past_key_value,
-                        new_tokens=None):
+                        new_tokens=None, tree=None):
         """Real-quant inference (realquant.pack_block): the same block with LayerNorm, biased PackedLinears and ReLU.
         new_tokens (the keyword of forward's **kwargs): the valid rows per sequence of a right-padded step on a ragged
         PackedKVCache (_cached_attention); a kvcache.PagedKVCache (paged, ragged storage; the caller creates it) is taken in
-        the same way."""
+        the same way.  tree (also through **kwargs): the step's rows are the nodes of a kvcache.TokenTree (a speculative tree
+        step, _cached_attention); OPT's positions live outside the block, so nothing is rotated."""
         self._packed_check(past_key_value, use_cache, output_attentions)
         if layer_head_mask is not None:
             raise NotImplementedError("the packed inference path runs without head masks")
@@ -155,12 +159,14 @@ class QuantOPTDecoderLayer(QuantBlockMixin, nn.Module):
         counts = self._new_tokens_in(new_tokens, past_key_value, bsz, T, x.device)
         # (KV-cache path, models/int_opt_layer.py:110-121,343-344: k / v appended to a PackedKVCache, returned as present)
         cache = self._kv_cache_in(past_key_value, bsz, T, nh, hd, x) if cached else None
+        if tree is not None:
+            self._tree_in(tree, cache, attention_mask, None, new_tokens, bsz, T, rope=False)
         h = self.self_attn_layer_norm(x) if self.do_layer_norm_before else x
         q = ops.ScaleFn.apply(a.q_proj(h), a.scaling).view(bsz, T, nh, hd)
         k = a.k_proj(h).view(bsz, T, nh, hd)
         v = a.v_proj(h).view(bsz, T, nh, hd)
         if cached:
-            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0, new_tokens=counts)
+            attn = self._cached_attention(q, k, v, cache, attention_mask, 1.0, new_tokens=counts, tree=tree)
         else:
             attn = self._packed_attention(q, k, v, attention_mask, 1.0)
         x = a.out_proj(attn.reshape(bsz, T, self.embed_dim), residual=x)
