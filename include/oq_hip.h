@@ -575,6 +575,39 @@ int oq_kv_tree_commit(void* buf, int64_t row_bytes, int64_t layers, int64_t laye
                       const int32_t* table, int64_t max_pages, int64_t num_pages, int page_size, const int32_t* lens,
                       const int32_t* accept, int64_t Tq, void* stream);
 
+/*   Greedy verification (csrc/oq_lmhead.hip; the lm_head call and the argmax over its stored logits of the reference's
+ *      evaluation / generation path: main.py:130 `logits = lm.model.lm_head(hidden_states)` and the greedy
+ *      `logits.argmax(dim=-1)` of models/models_utils.py:411, without the [rows, vocab] logits tensor between them).  h [M][ld_h] holds M hidden rows of H elements after the caller's final norm,
+ *      w [V][ld_w] the head, row-major as nn.Linear.weight; both bf16 or both fp16 (dtype), contracted on the 16x16x32 MFMA with
+ *      fp32 accumulation.  idx[m] = the lowest v that maximises sum_k h[m][k] w[v][k], val[m] = that maximum in fp32; equal head
+ *      rows give bit-equal logits, so ties are decided by index alone, and the result is bit-identical run to run (no atomics).
+ *      logits: NULL, or float [M][V] that also receives every logit (tests, callers that sample themselves).  One workgroup owns
+ *      a strip of vocabulary rows over all of H and every row tile of h, so the head is fetched once per call for M up to a row
+ *      tile and by one workgroup per strip beyond; (max, index) partials per (row, strip) go to the workspace
+ *      (oq_lm_head_workspace(M, V) bytes, 8-byte aligned) and a second launch folds them.  Rows >= M of the outputs are never
+ *      written; rows >= M of h and rows >= V of w are never read.  M >= 1, V >= 1, ld_h / ld_w >= H and multiples of 8, h / w
+ *      16-byte aligned.  A dtype other than bf16 / fp16 and an H that is not a multiple of 64 in [64, 16384] return
+ *      OQ_E_UNSUPPORTED; a null h / w / idx / val / workspace, a short workspace and bad sizes or strides OQ_E_ARG; nothing is
+ *      launched then.  Non-finite logits give an unspecified index in [0, V). */
+int64_t oq_lm_head_workspace(int64_t M, int64_t V);
+int oq_lm_head_argmax(const void* h, const void* w, int dtype, int64_t M, int64_t V, int64_t H, int64_t ld_h, int64_t ld_w,
+                      int32_t* idx, float* val, float* logits, void* workspace, int64_t workspace_bytes, void* stream);
+/*   Greedy acceptance over a token tree, fused with the fold of the strip partials: two launches for a whole verification.  h
+ *      holds the bs * Tq rows of a tree step (row b * Tq + t = node t of sequence b), anc / anc_bs are oq_attn_tree's ancestor
+ *      words, draft int32 [bs][Tq] the drafted token of every node (-1: padding), expect int32 [bs] or NULL the token the model
+ *      chose after the committed past (the previous step's next_token).  target[b][t] / target_val[b][t] = the argmax / max of
+ *      node t's row (the model's greedy token after node t).  A node is a match iff its draft is >= 0 and equals its parent's
+ *      target, or for a root expect[b] (any draft >= 0 when expect is NULL); it is accepted iff every node of its ancestor set is a
+ *      match.  best = the accepted node of largest depth, the lowest id among equals: accept[b][:] = its root path in ascending
+ *      order padded with -1 (oq_kv_tree_commit's accept), counts[b] = the path's length, next_token[b] = target[b][best]; with
+ *      no accepted node counts[b] = 0 and next_token[b] = expect[b], or -1 when expect is NULL.  Workspace:
+ *      oq_lm_head_workspace(bs * Tq, V).  Tq > 64 returns OQ_E_UNSUPPORTED, Tq < 1, anc_bs outside {1, bs} and a null pointer
+ *      other than expect OQ_E_ARG; the rest as oq_lm_head_argmax.  Nothing is launched on a refusal. */
+int oq_tree_verify_greedy(const void* h, const void* w, int dtype, int64_t bs, int Tq, int64_t V, int64_t H, int64_t ld_h,
+                          int64_t ld_w, const int32_t* anc, int64_t anc_bs, const int32_t* draft, const int32_t* expect,
+                          int32_t* accept, int32_t* counts, int32_t* next_token, int32_t* target, float* target_val,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused causal attention(models/int_llama_layer.py:143-163 and its autograd; bf16, head_dim 128, exact
  *      causal mask, T == 128 or T % 256 == 0 -- oq_attn_supported() says whether a problem qualifies; everything else keeps using
  *      oq_gemm + oq_softmax_*).  q, o, go [bs,T,nh,hd]; k, v [bs,T,nkv,hd] (q/k/v already fake-quantised by the caller,

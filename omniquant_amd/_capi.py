@@ -133,6 +133,10 @@ SIGNATURES = {
     "oq_attn_tree": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _i64,
                      _vp, _i64, _f32, _vp, _i64, _vp],
     "oq_kv_tree_commit": [_vp, _i64, _i64, _i64, _i64, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp],
+    # greedy verification: the LM head reduced to (max, argmax) per row, and the accepted root path of a token tree
+    "oq_lm_head_argmax": [_vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
+    "oq_tree_verify_greedy": [_vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _i64, _vp],
     "oq_sum_vectors": [_i32, _vp, _vp, _vp, _vp, _vp],
     "oq_cast": [_vp, _i32, _vp, _i32, _i64, _vp],
     "oq_let_vectors_fwd": [_i64] + [_vp] * 28,
@@ -175,7 +179,8 @@ SIZE_FUNCS = {"oq_fakequant_bwd_workspace": [_i64, _i64], "oq_norm_bwd_workspace
               "oq_fakequant_codes_supported": [_i64, _i64, _i32, _i32], "oq_packed_gemv_workspace": [_i64, _i64, _i64, _i32],
               "oq_packed_gemv_a4_workspace": [_i64, _i64, _i64],
               "oq_attn_decode_workspace": [_i64, _i32, _i32, _i64, _i64, _i32],
-              "oq_attn_extend_workspace": [_i64, _i32, _i32, _i64, _i64, _i32], "oq_attn_extend_supported": [_i32, _i64, _i32]}
+              "oq_attn_extend_workspace": [_i64, _i32, _i32, _i64, _i64, _i32], "oq_attn_extend_supported": [_i32, _i64, _i32],
+              "oq_lm_head_workspace": [_i64, _i64]}
 
 _lib = None
 

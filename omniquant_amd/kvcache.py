@@ -139,6 +139,41 @@ class TokenTree:
             prev = n
         return True
 
+    def greedy_accept(self, draft, target, expect=None):
+        """Greedy acceptance on the host, the rule of ops.tree_verify_greedy (csrc/oq_lmhead.hip) on lists.  draft[b][t]: the
+        drafted token of node t (-1: a padding node), target[b][t]: the model's greedy token after node t, expect[b] (or None):
+        the token the model chose after the committed past.  A node matches iff its draft is >= 0 and equals its parent's target
+        (a root: expect[b], or anything when expect is None); it is accepted iff it and all its ancestors match.  The accepted
+        node of largest depth wins, the lowest id among equals.  Returns (paths, next_tokens): per sequence the winner's root
+        path (ascending node ids; [] if no node is accepted) and target[b][winner] (expect[b], or -1 without expect, if none)."""
+        try:
+            draft = [[operator.index(x) for x in row] for row in draft]
+            target = [[operator.index(x) for x in row] for row in target]
+            expect = None if expect is None else [operator.index(x) for x in expect]
+        except TypeError:
+            raise OQError("TokenTree.greedy_accept: draft and target are bs lists of Tq ints, expect bs ints or None") from None
+        bs = len(draft)
+        if self.bs not in (None, bs):
+            raise OQError(f"TokenTree.greedy_accept: {self!r} for a batch of {bs}")
+        if len(target) != bs or (expect is not None and len(expect) != bs) or any(len(r) != self.Tq for r in draft + target):
+            raise OQError(f"TokenTree.greedy_accept: draft and target must be {bs} rows of {self.Tq} tokens, expect {bs} tokens")
+        paths, nexts = [], []
+        for b in range(bs):
+            i = self._tree(b)
+            par, depth = self._trees[i], self._depth[i]
+            accepted, best = [], -1
+            for t in range(self.Tq):
+                if par[t] < 0:
+                    ok = draft[b][t] >= 0 and (expect is None or draft[b][t] == expect[b])
+                else:
+                    ok = draft[b][t] >= 0 and accepted[par[t]] and draft[b][t] == target[b][par[t]]
+                accepted.append(ok)
+                if ok and (best < 0 or depth[t] > depth[best]):
+                    best = t
+            paths.append(self.path(best, b) if best >= 0 else [])
+            nexts.append(target[b][best] if best >= 0 else (-1 if expect is None else expect[b]))
+        return paths, nexts
+
     def to(self, device):
         """The tree on `device` (uploaded once, then cached): an object with anc int32 [1 | bs, Tq, 2] and depth int64
         [1 | bs, Tq]."""

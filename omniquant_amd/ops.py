@@ -2196,6 +2196,129 @@ def kv_tree_commit(buffer, lengths, accept, page_table=None):
     return buffer
 
 
+def _head_rows(fn, name, t, H=None):
+    """A [rows, H] operand of the LM-head kernels: (tensor that holds it, rows, H, leading dimension).  A 2-D view whose rows are
+    contiguous and a multiple of 8 elements apart is taken as it is (its padding is never read); anything else is copied."""
+    if not torch.is_tensor(t) or t.dim() < 1:
+        raise C.OQError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise C.OQError(f"{fn}: {name} on {t.device}: the LM-head kernels need GPU tensors; there is no CPU fallback")
+    if t.dtype not in (torch.bfloat16, torch.float16):
+        raise C.OQError(f"{fn}: {name} is {t.dtype} (bfloat16 or float16, the same for h and the head)")
+    if H is not None and t.shape[-1] != H:
+        raise C.OQError(f"{fn}: {name} {tuple(t.shape)} does not fit a hidden size of {H}")
+    H = t.shape[-1]
+    if H % 64 != 0 or not 64 <= H <= 16384:
+        raise C.OQError(f"{fn}: hidden size {H} (a multiple of 64 from 64 to 16384)")
+    if not (t.dim() == 2 and t.stride(1) == 1 and (t.shape[0] == 1 or (t.stride(0) >= H and t.stride(0) % 8 == 0))):
+        t = t.reshape(-1, H).contiguous()
+    rows = t.shape[0]
+    if rows < 1:
+        raise C.OQError(f"{fn}: {name} {tuple(t.shape)} has no rows")
+    if t.data_ptr() % 16 != 0:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t, rows, H, (t.stride(0) if rows > 1 else H)
+
+
+def _head_workspace(M, V, workspace, device):
+    ws_n = C.size_call("oq_lm_head_workspace", M, V)
+    if workspace is not None and (not torch.is_tensor(workspace) or workspace.device != device or not workspace.is_contiguous()):
+        raise C.OQError(f"lm head: workspace must be a contiguous tensor on {device}")
+    if workspace is None or workspace.numel() * workspace.element_size() < ws_n or workspace.data_ptr() % 8 != 0:
+        workspace = torch.empty(max(ws_n, 16), dtype=torch.uint8, device=device)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def lm_head_workspace(M, V):
+    """Bytes of workspace lm_head_argmax / tree_verify_greedy use for M rows over a vocabulary of V (oq_lm_head_workspace)."""
+    return C.size_call("oq_lm_head_workspace", int(M), int(V))
+
+
+def lm_head_argmax(h, weight, out=None, logits=None, workspace=None):
+    """Greedy token of every row without storing logits (oq_lm_head_argmax, csrc/oq_lmhead.hip): h [..., H] hidden rows after the
+    final norm, weight [V, H] the head as nn.Linear.weight, both bfloat16 or both float16.  Returns (idx int32, val float32)
+    shaped like h without its last dimension: idx = the lowest index of the row's largest logit h @ weight.T (fp32
+    accumulation on the MFMA), val = that logit.  out: an (idx, val) pair to write into; logits: a float32 [..., V] tensor that
+    also receives every logit; workspace: a device byte buffer of lm_head_workspace(M, V) bytes to reuse (one is allocated if it
+    is missing or too small).  2-D views with padded rows (stride a multiple of 8 elements) are read in place."""
+    fn = "lm_head_argmax"
+    lead = tuple(h.shape[:-1]) if torch.is_tensor(h) else ()
+    h2, M, H, ld_h = _head_rows(fn, "h", h)
+    w2, V, _, ld_w = _head_rows(fn, "weight", weight, H)
+    if weight.dim() != 2:
+        raise C.OQError(f"{fn}: weight must be [V, H], got {tuple(weight.shape)}")
+    if w2.dtype != h2.dtype or w2.device != h2.device:
+        raise C.OQError(f"{fn}: h is {h2.dtype} on {h2.device}, weight {w2.dtype} on {w2.device}")
+    if out is None:
+        idx = torch.empty(lead, dtype=torch.int32, device=h2.device)
+        val = torch.empty(lead, dtype=torch.float32, device=h2.device)
+    else:
+        idx, val = out
+        for t, dt, name in ((idx, torch.int32, "idx"), (val, torch.float32, "val")):
+            if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != lead or t.device != h2.device or not t.is_contiguous():
+                raise C.OQError(f"{fn}: out {name} must be a contiguous {dt} {lead} tensor on {h2.device}")
+    if logits is not None and (not torch.is_tensor(logits) or logits.dtype != torch.float32 or tuple(logits.shape) != lead + (V,)
+                               or logits.device != h2.device or not logits.is_contiguous()):
+        raise C.OQError(f"{fn}: logits must be a contiguous float32 {lead + (V,)} tensor on {h2.device}")
+    workspace, ws_n = _head_workspace(M, V, workspace, h2.device)
+    C.call("oq_lm_head_argmax", h2.data_ptr(), w2.data_ptr(), C.dt(h2), M, V, H, ld_h, ld_w, C.ptr(idx), C.fptr(val), C.fptr(logits),
+           C.ptr(workspace), ws_n, C.stream())
+    return idx, val
+
+
+def tree_verify_greedy(h, weight, tree, draft, expect=None, workspace=None):
+    """Greedy verification of a speculative tree step in two launches (oq_tree_verify_greedy, csrc/oq_lmhead.hip), nothing read
+    by the host.  h [bs, Tq, H]: the tree step's output rows after the final norm (row t = node t); weight [V, H] the head; both
+    bfloat16 or both float16.  tree: the step's kvcache.TokenTree (or its int32 [1 | bs, Tq, 2] anc tensor on the device); draft
+    int32 [bs, Tq] on the device, the drafted token of every node, -1 for padding nodes (a sequence whose drafts are all -1 is
+    inactive); expect int32 [bs] on the device, the token the model chose after the committed past (the previous step's
+    next_token), or None to admit every root.  The rule is TokenTree.greedy_accept's.  Returns (accept int32 [bs, Tq] for
+    commit_tree, counts int32 [bs], next_token int32 [bs], target int32 [bs, Tq], target_val float32 [bs, Tq])."""
+    fn = "tree_verify_greedy"
+    if not torch.is_tensor(h) or h.dim() != 3:
+        raise C.OQError(f"{fn}: h must be a [bs, Tq, H] tensor")
+    if not h.is_cuda:
+        raise C.OQError(f"{fn}: h on {h.device}: the verification needs GPU tensors; there is no CPU fallback")
+    bs, Tq, _ = h.shape
+    if not 1 <= Tq <= 64:
+        raise C.OQError(f"{fn}: Tq {Tq} (a token tree has 1 to 64 nodes)")
+    h2, M, H, ld_h = _head_rows(fn, "h", h)
+    w2, V, _, ld_w = _head_rows(fn, "weight", weight, H)
+    if weight.dim() != 2:
+        raise C.OQError(f"{fn}: weight must be [V, H], got {tuple(weight.shape)}")
+    if w2.dtype != h2.dtype or w2.device != h2.device:
+        raise C.OQError(f"{fn}: h is {h2.dtype} on {h2.device}, weight {w2.dtype} on {w2.device}")
+    from .kvcache import TokenTree
+    if isinstance(tree, TokenTree):
+        if tree.bs not in (None, bs):
+            raise C.OQError(f"{fn}: {tree!r} for a batch of {bs}")
+        anc = tree.to(h.device).anc
+    elif torch.is_tensor(tree):
+        anc = tree
+    else:
+        raise C.OQError(f"{fn}: tree must be a kvcache.TokenTree or its int32 [1 | {bs}, {Tq}, 2] anc tensor, got {type(tree).__name__}")
+    if anc.dtype != torch.int32 or anc.dim() != 3 or anc.shape[0] not in (1, bs) or tuple(anc.shape[1:]) != (Tq, 2):
+        raise C.OQError(f"{fn}: the tree's ancestor sets {tuple(anc.shape)} {anc.dtype} (int32 [1 | {bs}, {Tq}, 2]: a tree of the "
+                        "step's Tq nodes)")
+    if anc.device != h.device:
+        raise C.OQError(f"{fn}: the tree's ancestor sets on {anc.device}, h on {h.device}")
+    if not torch.is_tensor(draft) or draft.dtype != torch.int32 or tuple(draft.shape) != (bs, Tq) or draft.device != h.device:
+        what = f"{tuple(draft.shape)} {draft.dtype} on {draft.device}" if torch.is_tensor(draft) else type(draft).__name__
+        raise C.OQError(f"{fn}: draft must be an int32 [{bs}, {Tq}] tensor on {h.device}, got {what}")
+    if expect is not None and (not torch.is_tensor(expect) or expect.dtype != torch.int32 or tuple(expect.shape) != (bs,)
+                               or expect.device != h.device):
+        what = f"{tuple(expect.shape)} {expect.dtype} on {expect.device}" if torch.is_tensor(expect) else type(expect).__name__
+        raise C.OQError(f"{fn}: expect must be None or an int32 [{bs}] tensor on {h.device}, got {what}")
+    workspace, ws_n = _head_workspace(M, V, workspace, h.device)
+    i32 = dict(dtype=torch.int32, device=h.device)
+    accept, counts, next_token = torch.empty(bs, Tq, **i32), torch.empty(bs, **i32), torch.empty(bs, **i32)
+    target, target_val = torch.empty(bs, Tq, **i32), torch.empty(bs, Tq, dtype=torch.float32, device=h.device)
+    C.call("oq_tree_verify_greedy", h2.data_ptr(), w2.data_ptr(), C.dt(h2), bs, Tq, V, H, ld_h, ld_w, C.ptr(anc.contiguous()),
+           anc.shape[0], C.ptr(draft.contiguous()), None if expect is None else C.ptr(expect.contiguous()), C.ptr(accept),
+           C.ptr(counts), C.ptr(next_token), C.ptr(target), C.fptr(target_val), C.ptr(workspace), ws_n, C.stream())
+    return accept, counts, next_token, target, target_val
+
+
 def _kv_pages_args(fn, pool, ids, flat=None, flat_name=None):
     """Validate a page move of a model-wide pool (kvcache.PagedKVPool), on the host and before any device call: `ids` =
     ((name, tensor), ...) are int32 1-D tensors of one length on the pool's device, `pool` a contiguous [layers, num_pages, ...]
